@@ -8,6 +8,7 @@ the work per token does not depend on the chunk).  Every call goe
 records around the GEMM launch).  Inputs (activations, packed weights) are resident in HBM before the timed region.
 
   python bench.py --gpus N --steps K --warmup W           (N>1: launched by torch.distributed.run, one rank per GPU)
+  python bench.py ... --dump-outputs DIR                  (also writes the last timed step's outputs, see dump_last_step_outputs)
 
 Multi-GPU: the path partitions over tokens with no data-path collective (each rank owns a full copy of the 4.6 GB of
 packed weights and its own token stream) -> default "dp", weak scaling.  `--tp T` runs the north-star TP layout
@@ -622,6 +623,27 @@ class Model:
         self.calls, self.keep = [], []
 
 
+DUMP_ROWS = 256   # rows sampled per output: 256 x (12288 + 11008 + 4096) float32 = 28 MB for Llama-2-7B (the cap is 64 MB)
+
+
+def dump_last_step_outputs(model, chunk, out_dir):
+    """The outputs the timed path returned in its last step, as float32 .npy: for every linear of the model, the output of its
+    last call (the last layer, the last M-chunk) -- what is still resident when the step ends; at tp > 1 the gathered tensor.
+    Rows: a fixed, seeded sample of DUMP_ROWS of the chunk (all of them when the chunk is smaller); the inputs come from the
+    seeded generator, so the same arguments give the same inputs on every run."""
+    rows = np.sort(np.random.default_rng(0).choice(chunk, size=min(DUMP_ROWS, chunk), replace=False))
+    idx = torch.from_numpy(rows).to(model.dev)
+    names = [name for name, _, _ in model.spec["linears"]]
+    total = 0
+    for name, call in zip(names, model.calls[-len(names):]):   # the calls of the last layer
+        outs, N = call[7], call[8]
+        out = model.full[N] if model.tp > 1 else outs[0]
+        sample = out.index_select(0, idx).float().cpu().numpy()
+        total += sample.nbytes
+        assert total <= 64 << 20, "--dump-outputs: more than 64 MB"
+        np.save(os.path.join(out_dir, f"{name}.npy"), sample)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -648,7 +670,12 @@ def main():
     ap.add_argument("--no-config5", action="store_true", help="tp = N leg: skip BASELINE configs[4] (Llama-2-70B, rows of W sharded N ways + the all-gather)")
     ap.add_argument("--config5-layers", type=int, default=80, help="decoder layers of the Llama-2-70B leg (80 = the model; the one-GPU tests run 1)")
     ap.add_argument("--variant", type=int, default=0, help="GEMM schedule: 0 auto, 1 two-barrier, 2 ping-pong (A/B runs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as DIR/<linear>.npy (float32, a fixed "
+                         "seeded sample of rows; rank 0) so that two builds can be compared output for output")
     args = ap.parse_args()
+    if args.dump_outputs:   # fail before anything is measured, not after
+        os.makedirs(args.dump_outputs, exist_ok=True)
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ and "RANK" not in os.environ:
         # `python bench.py --gpus N ...` typed as is (the reference's multi-GPU scripts self-launch too,
@@ -806,6 +833,8 @@ def main():
     if tp > 1:
         model.open_peer_transport(parallel, tp_rank, tp_group)
     elapsed, median_ms, events, launches_per_step = timed_run(model, tp_group, args.steps, args.warmup, True)
+    if args.dump_outputs and rank == 0:   # before any later leg reuses the output buffers
+        dump_last_step_outputs(model, chunk, args.dump_outputs)
 
     # ---- roofline of the dominant kernel (fused int8 GEMM), from the events recorded inside the timed region ----
     gemm_ms = 0.0

@@ -44,8 +44,16 @@ def test_small_tile_split_gives_the_bits_of_the_one_workgroup_form(lib, factor, 
     assert lib.mixq_gemm_mixed(p(qA), p(W), p(sA), p(sW), fa, fw, p(ref), M, N, K, O, st) == 0
     lib.mixq_debug_set_gemm_variant(60 + factor)
     n = lib.mixq_gemm_scratch_size(M, N, K)
-    if n == 0:
-        pytest.skip("this factor does not apply to the shape (too many tiles)")
+    if n == 0:   # the factor does not apply to the shape (too many tiles): even offered scratch, the one-workgroup form runs
+        nb = lib.mixq_gemm_scratch_bound()
+        scr = torch.zeros(nb, dtype=torch.uint8, device="cuda:0")
+        out = torch.full((M, N), float("nan"), dtype=torch.float16, device="cuda:0")
+        assert lib.mixq_gemm_mixed_scratch(p(qA), p(W), p(sA), p(sW), fa, fw, p(out), M, N, K, O, p(scr), nb, st) == 0
+        torch.cuda.synchronize()
+        kern = lib.mixq_debug_last_gemm_kernel()
+        assert not (kern.startswith(b"two-barrier") and b"along K" in kern), kern
+        assert torch.equal(out, ref)
+        return
     scr = torch.zeros(n, dtype=torch.uint8, device="cuda:0")
     for round_ in range(4):   # the counter of every tile is left zero by the last workgroup
         out = torch.full((M, N), float("nan"), dtype=torch.float16, device="cuda:0")
