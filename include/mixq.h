@@ -129,6 +129,16 @@ MIXQ_API int mixq_enqueue_profiled(const mixq_handle* h, const mixq_tensor_desc*
                                    const mixq_tensor_desc* outputDesc, const void* const* inputs, void* const* outputs,
                                    void* workspace, void* stream, void* ev_gemm_start, void* ev_gemm_stop);
 
+/* mixq_enqueue with the layer's bias added in the GEMM's epilogue (MI355X extension, ABI revision 5).  Replaces the fp16 add the
+ * reference puts in the TensorRT graph after the plugin (plugin.py:158-160: x = x + cast(bias, x.dtype)): bias_f16 is fp16 [N],
+ * and every output element is fp16(float(out) + float(bias[n])) of the value mixq_enqueue writes -- bit-identical to mixq_enqueue
+ * followed by an fp16 add, without the second pass over the output.  Same kernels as mixq_enqueue for every shape, same
+ * workspace; no allocation, no synchronisation (HIP-graph capturable).  bias_f16 == NULL: exactly mixq_enqueue.  A bias that
+ * is not 16-byte aligned returns MIXQ_E_ALIGN before anything is launched. */
+MIXQ_API int mixq_enqueue_bias(const mixq_handle* h, const mixq_tensor_desc* inputDesc, const mixq_tensor_desc* outputDesc,
+                               const void* const* inputs, void* const* outputs, const void* bias_f16, void* workspace,
+                               void* stream);
+
 /* ---- launcher level (kernel/int8FusedDequantizeCUDA.h:3-27, weightonlykernel/fpA_intB_gemm_wrapper.h:8-11) ----- */
 /* int8quant (kernel/i8gemm.cu:139-150): per-row fp16 amax/127 scale + int8 quantisation. */
 MIXQ_API int mixq_int8quant(int rows, int cols, const void* src_f16, int8_t* output, void* scale_f16, void* stream);
@@ -192,6 +202,12 @@ MIXQ_API size_t mixq_gemm_scratch_bound(void);
 MIXQ_API int mixq_gemm_mixed_scratch(const int8_t* qA, const int8_t* W, const void* sA, const void* sW, const void* fpA,
                                      const void* fpW, void* Out, int M, int N, int K, int O, void* scratch,
                                      size_t scratch_bytes, void* stream);
+/* mixq_gemm_mixed_scratch with the layer's fp16 [N] bias (16-byte aligned, not NULL) added to the rounded result in the epilogue:
+ * bit-identical to mixq_gemm_mixed_scratch followed by an fp16 add (the reference's plugin.py:158-160), the same kernel for every
+ * shape.  O <= 128 (one LDS pass of outlier columns), else MIXQ_E_SHAPE. */
+MIXQ_API int mixq_gemm_mixed_bias(const int8_t* qA, const int8_t* W, const void* sA, const void* sW, const void* fpA,
+                                  const void* fpW, const void* bias, void* Out, int M, int N, int K, int O, void* scratch,
+                                  size_t scratch_bytes, void* stream);
 /* ---- weight images (MI355X extension; no reference counterpart, no result changes) -----------------------------------------
  * The reference stores `weight` (inputs[1]) row-major int8 [N, K].  Decode batches (5 .. 64 rows) are weight streams, and the
  * weight-streaming GEMM's MFMA fragment load takes 64 bytes of 16 rows that lie K bytes apart.  A runtime that can spare N * K
@@ -454,6 +470,12 @@ MIXQ_API int mixq_tp_fused_supported(int64_t M, int64_t N_local, int64_t K);
 MIXQ_API int mixq_tp_flag_words(int64_t M);
 MIXQ_API int mixq_enqueue_tp(const mixq_handle* h, const mixq_tensor_desc* inputDesc, const void* const* inputs,
                              void* workspace, const mixq_tp_epilogue* tp, void* stream);
+/* mixq_enqueue_tp with this rank's [N_local] slice of the layer's fp16 bias added before its columns are written (ABI revision 5):
+ * the gathered result is bit-identical to mixq_enqueue + the fp16 add of the full bias (plugin.py:158-160) + the gather.  Same
+ * preconditions and codes as mixq_enqueue_tp (MIXQ_E_SHAPE where mixq_tp_fused_supported is 0); a bias that is not 16-byte
+ * aligned returns MIXQ_E_ALIGN; NULL: exactly mixq_enqueue_tp. */
+MIXQ_API int mixq_enqueue_tp_bias(const mixq_handle* h, const mixq_tensor_desc* inputDesc, const void* const* inputs,
+                                  const void* bias_f16, void* workspace, const mixq_tp_epilogue* tp, void* stream);
 
 /* ---- host helpers ----------------------------------------------------------------------------- */
 /* preprocess_weights (weightonlykernel/cutlass_kernels/cutlass_preprocessors.cc:536-545), int8, arch 80-90:
@@ -499,8 +521,9 @@ MIXQ_API const char* mixq_version(void);
 /* ABI revision of THIS header.  It is bumped whenever an exported entry changes its argument list in place (revision 3: the
  * mixq_tp_buffer_alloc / mixq_tp_push_columns / mixq_tp_wait signatures of round 3), so that a host built against an older
  * header can refuse to run instead of passing shifted arguments: `if (mixq_abi_version() != MIXQ_ABI_VERSION) fail`.  The
- * reference-named entries (initOpenAiTritonPlugins, the plugin lifecycle, mixq_enqueue) have not changed since revision 1. */
-#define MIXQ_ABI_VERSION 4
+ * reference-named entries (initOpenAiTritonPlugins, the plugin lifecycle, mixq_enqueue) have not changed since revision 1.
+ * Revision 5 adds entries only (mixq_enqueue_bias, mixq_enqueue_tp_bias, mixq_gemm_mixed_bias). */
+#define MIXQ_ABI_VERSION 5
 MIXQ_API int mixq_abi_version(void);
 MIXQ_API const char* mixq_error_string(int code);
 

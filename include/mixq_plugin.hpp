@@ -73,6 +73,13 @@ public:
     {
         return mixq_enqueue(h_, inputDesc, outputDesc, inputs, outputs, workspace, stream);
     }
+    /* enqueue with the layer's fp16 [N] bias added in the GEMM's epilogue (mixq_enqueue_bias: bit-identical to enqueue followed by
+     * the fp16 add the reference places after the plugin, plugin.py:158-160; NULL = enqueue) */
+    int enqueueWithBias(const PluginTensorDesc* inputDesc, const PluginTensorDesc* outputDesc, const void* const* inputs,
+                        void* const* outputs, const void* bias_f16, void* workspace, void* stream) const noexcept
+    {
+        return mixq_enqueue_bias(h_, inputDesc, outputDesc, inputs, outputs, bias_f16, workspace, stream);
+    }
     /* IPluginV2Ext */
     int getOutputDataType(int index, const int* /*inputTypes*/, int /*nbInputs*/) const noexcept /* .cpp:768-773 */
     {

@@ -85,6 +85,8 @@ SIGNATURES = {
     "mixq_enqueue_scratch_size": (_sz, [_i64, _i64, _i64]),
     "mixq_enqueue": (_i, [_vp, ctypes.POINTER(TensorDesc), ctypes.POINTER(TensorDesc), ctypes.POINTER(_vp),
                           ctypes.POINTER(_vp), _vp, _vp]),
+    "mixq_enqueue_bias": (_i, [_vp, ctypes.POINTER(TensorDesc), ctypes.POINTER(TensorDesc), ctypes.POINTER(_vp),
+                               ctypes.POINTER(_vp), _vp, _vp, _vp]),
     "mixq_weight_image_bytes": (_sz, [_i64, _i64]),
     "mixq_weight_image_register": (_i, [_vp, _i64, _i64, _vp, _vp]),
     "mixq_weight_image_unregister": (_i, [_vp]),
@@ -116,6 +118,7 @@ SIGNATURES = {
     "mixq_gemm_scratch_size": (ctypes.c_size_t, [_i, _i, _i]),
     "mixq_gemm_scratch_bound": (ctypes.c_size_t, []),
     "mixq_gemm_mixed_scratch": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, ctypes.c_size_t, _vp]),
+    "mixq_gemm_mixed_bias": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, ctypes.c_size_t, _vp]),
     "mixq_int8_fused_dequantize_silu_mul": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
     "mixq_gemm_mixed": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "mixq_mixlinear_forward": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, ctypes.c_size_t, _vp]),
@@ -147,6 +150,7 @@ SIGNATURES = {
     "mixq_tp_fused_supported": (_i, [_i64, _i64, _i64]),
     "mixq_tp_flag_words": (_i, [_i64]),
     "mixq_enqueue_tp": (_i, [_vp, ctypes.POINTER(TensorDesc), ctypes.POINTER(_vp), _vp, ctypes.POINTER(TpEpilogue), _vp]),
+    "mixq_enqueue_tp_bias": (_i, [_vp, ctypes.POINTER(TensorDesc), ctypes.POINTER(_vp), _vp, _vp, ctypes.POINTER(TpEpilogue), _vp]),
     "mixq_preprocess_weights_int8": (_i, [_vp, _vp, _sz, _sz]),
     "mixq_unprocess_weights_int8": (_i, [_vp, _vp, _sz, _sz]),
     "mixq_debug_set_gemm_variant": (None, [_i]),
@@ -162,7 +166,7 @@ SIGNATURES = {
 }
 
 _lib = None
-ABI_VERSION = 4   # include/mixq.h MIXQ_ABI_VERSION
+ABI_VERSION = 5   # include/mixq.h MIXQ_ABI_VERSION
 
 
 def load():

@@ -32,11 +32,14 @@ __device__ __forceinline__ v2h dequant_pair(unsigned w, unsigned sel, v2h scale2
 
 // PPW column pairs per wave share every activation load (for M > 1 the activation re-reads through the L1/TA path,
 // not HBM, are what limits a one-pair-per-wave kernel); WPP waves share the K range of their pairs.
-template <int MB, int WPP, int PPW>
+// BIAS: Out = fp16(fp16(sum) + bias[n]) -- the layer's bias (fp16 [N]) added to the rounded result, requested by the storing lanes
+// behind the reduction (requested with the scales, its registers through the loop cost one wave per SIMD).
+template <int MB, int WPP, int PPW, bool BIAS = false>
 __global__ __launch_bounds__(256) void w8a16_gemv_kernel(const uint16_t* __restrict__ A,
                                                           const uint8_t* __restrict__ Wq,
                                                           const uint16_t* __restrict__ scale,
-                                                          uint16_t* __restrict__ Out, int N, int K)
+                                                          uint16_t* __restrict__ Out, int N, int K,
+                                                          const uint16_t* __restrict__ bias)
 {
     constexpr int GPB = 4 / WPP; // pair groups per block
     __shared__ float red[4][PPW][MB][2];
@@ -137,37 +140,38 @@ __global__ __launch_bounds__(256) void w8a16_gemv_kernel(const uint16_t* __restr
 #pragma unroll
                         for (int w2 = 0; w2 < WPP; ++w2) s += red[wave + w2][q][m][col];
                     }
-                    Out[(int64_t)m * N + n] = f2h_bits(s);
+                    if constexpr (BIAS) Out[(int64_t)m * N + n] = hadd_bits(f2h_bits(s), bias[n]);
+                    else Out[(int64_t)m * N + n] = f2h_bits(s);
                 }
             }
         }
     }
 }
 
-template <int MB, int PPW>
+template <int MB, int PPW, bool BIAS>
 static hipError_t launch_mb(const uint16_t* A, const uint8_t* Wq, const uint16_t* scale, uint16_t* Out, int N, int K,
-                            hipStream_t st)
+                            hipStream_t st, const uint16_t* bias)
 {
     const int groups = (N / 2 + PPW - 1) / PPW;
     // aim for >= 4096 waves while keeping >= 2 KiB of each pair's weights per wave
     int wpp = 1;
     while (wpp < 4 && groups * wpp < 4096 && (2 * K) / (wpp * 2) >= 2048) wpp *= 2;
     if (wpp == 4) {
-        hipLaunchKernelGGL((w8a16_gemv_kernel<MB, 4, PPW>), dim3((unsigned)groups), dim3(256), 0, st, A, Wq, scale, Out, N, K);
+        hipLaunchKernelGGL((w8a16_gemv_kernel<MB, 4, PPW, BIAS>), dim3((unsigned)groups), dim3(256), 0, st, A, Wq, scale, Out, N, K, bias);
     } else if (wpp == 2) {
-        hipLaunchKernelGGL((w8a16_gemv_kernel<MB, 2, PPW>), dim3((unsigned)((groups + 1) / 2)), dim3(256), 0, st, A, Wq,
-                           scale, Out, N, K);
+        hipLaunchKernelGGL((w8a16_gemv_kernel<MB, 2, PPW, BIAS>), dim3((unsigned)((groups + 1) / 2)), dim3(256), 0, st, A, Wq,
+                           scale, Out, N, K, bias);
     } else {
-        hipLaunchKernelGGL((w8a16_gemv_kernel<MB, 1, PPW>), dim3((unsigned)((groups + 3) / 4)), dim3(256), 0, st, A, Wq,
-                           scale, Out, N, K);
+        hipLaunchKernelGGL((w8a16_gemv_kernel<MB, 1, PPW, BIAS>), dim3((unsigned)((groups + 3) / 4)), dim3(256), 0, st, A, Wq,
+                           scale, Out, N, K, bias);
     }
     return hipGetLastError();
 }
 
-hipError_t launch_w8a16(const void* A, const uint8_t* Wq, const void* scale, void* Out, int M, int N, int K,
-                        hipStream_t st)
+template <bool BIAS>
+static hipError_t launch_w8a16_rows(const void* A, const uint8_t* Wq, const void* scale, void* Out, int M, int N, int K,
+                                    hipStream_t st, const uint16_t* bias)
 {
-    if (M <= 0 || N <= 0) return hipSuccess;
     const uint16_t* a = static_cast<const uint16_t*>(A);
     const uint16_t* s = static_cast<const uint16_t*>(scale);
     uint16_t* o = static_cast<uint16_t*>(Out);
@@ -175,14 +179,22 @@ hipError_t launch_w8a16(const void* A, const uint8_t* Wq, const void* scale, voi
         const int mb = (M - m0) < 4 ? (M - m0) : 4;
         hipError_t e;
         switch (mb) {
-        case 1: e = launch_mb<1, 1>(a + (int64_t)m0 * K, Wq, s, o + (int64_t)m0 * N, N, K, st); break;
-        case 2: e = launch_mb<2, 4>(a + (int64_t)m0 * K, Wq, s, o + (int64_t)m0 * N, N, K, st); break;
-        case 3: e = launch_mb<3, 4>(a + (int64_t)m0 * K, Wq, s, o + (int64_t)m0 * N, N, K, st); break;
-        default: e = launch_mb<4, 4>(a + (int64_t)m0 * K, Wq, s, o + (int64_t)m0 * N, N, K, st); break;
+        case 1: e = launch_mb<1, 1, BIAS>(a + (int64_t)m0 * K, Wq, s, o + (int64_t)m0 * N, N, K, st, bias); break;
+        case 2: e = launch_mb<2, 4, BIAS>(a + (int64_t)m0 * K, Wq, s, o + (int64_t)m0 * N, N, K, st, bias); break;
+        case 3: e = launch_mb<3, 4, BIAS>(a + (int64_t)m0 * K, Wq, s, o + (int64_t)m0 * N, N, K, st, bias); break;
+        default: e = launch_mb<4, 4, BIAS>(a + (int64_t)m0 * K, Wq, s, o + (int64_t)m0 * N, N, K, st, bias); break;
         }
         if (e != hipSuccess) return e;
     }
     return hipSuccess;
+}
+
+hipError_t launch_w8a16(const void* A, const uint8_t* Wq, const void* scale, void* Out, int M, int N, int K,
+                        hipStream_t st, const void* bias)
+{
+    if (M <= 0 || N <= 0) return hipSuccess;
+    if (bias != nullptr) return launch_w8a16_rows<true>(A, Wq, scale, Out, M, N, K, st, static_cast<const uint16_t*>(bias));
+    return launch_w8a16_rows<false>(A, Wq, scale, Out, M, N, K, st, nullptr);
 }
 
 } // namespace mixq

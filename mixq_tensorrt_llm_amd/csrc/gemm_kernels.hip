@@ -266,15 +266,18 @@ __global__ __launch_bounds__(WAVES_M* WAVES_N* KG * 64) void gemm_w8a8o16_kernel
     // (the mid-M kernel's timeline priced the same pattern at 1.3 us per tile, profiles/r06_mid_v1_timeline.txt).  Clamped: rows / columns past
     // the edge are never stored.
     float sa_pre[TM];
-    uint2 sw_pre[TN][4];
+    uint2 sw_pre[TN][4], bias_pre[TN][4]; // (bias_pre: EPI_DEQUANT_BIAS only, requested with the weight scales)
     if (EPI != EPI_INT32) {
 #pragma unroll
         for (int j = 0; j < TM; ++j) sa_pre[j] = h2f(p.sA[min(m0 + wm * WM + j * 32 + lr, p.M - 1)]);
 #pragma unroll
         for (int i = 0; i < TN; ++i)
 #pragma unroll
-            for (int g = 0; g < 4; ++g)
-                sw_pre[i][g] = *reinterpret_cast<const uint2*>(p.sW + min(n0 + wn * WN + i * 32 + 4 * lh + 8 * g, p.N - 4));
+            for (int g = 0; g < 4; ++g) {
+                const int nb = min(n0 + wn * WN + i * 32 + 4 * lh + 8 * g, p.N - 4);
+                sw_pre[i][g] = *reinterpret_cast<const uint2*>(p.sW + nb);
+                if constexpr (EPI == EPI_DEQUANT_BIAS) bias_pre[i][g] = *reinterpret_cast<const uint2*>(p.bias + nb);
+            }
     }
 
     // ---- in-workgroup split-K: partial accumulators of groups 1.. -> LDS -> added by group 0 ----------
@@ -428,6 +431,13 @@ __global__ __launch_bounds__(WAVES_M* WAVES_N* KG * 64) void gemm_w8a8o16_kernel
                                                     (uint16_t)(mb.y & 0xffffu), (uint16_t)(mb.y >> 16)};
 #pragma unroll
                             for (int e = 0; e < 4; ++e) oh[e] = f2h_bits(h2f(oh[e]) * h2f(mh[e]));
+                        }
+                        if constexpr (EPI == EPI_DEQUANT_BIAS) { // the layer's bias: one fp16 add of the rounded result
+                            const uint2 bb = bias_pre[i][g];
+                            const uint16_t bh[4] = {(uint16_t)(bb.x & 0xffffu), (uint16_t)(bb.x >> 16), (uint16_t)(bb.y & 0xffffu),
+                                                    (uint16_t)(bb.y >> 16)};
+#pragma unroll
+                            for (int e = 0; e < 4; ++e) oh[e] = hadd_bits(oh[e], bh[e]);
                         }
                         uint2 o;
                         o.x = (unsigned)oh[0] | ((unsigned)oh[1] << 16);
@@ -630,6 +640,7 @@ hipError_t launch_gemm_deep(const GemmParams& p, int epi, hipStream_t st)
     case EPI_DEQUANT: return launch_deep_epi<EPI_DEQUANT>(p, st);
     case EPI_DEQUANT_SILU: return launch_deep_epi<EPI_DEQUANT_SILU>(p, st);
     case EPI_DEQUANT_SILU_MUL: return launch_deep_epi<EPI_DEQUANT_SILU_MUL>(p, st);
+    case EPI_DEQUANT_BIAS: return launch_deep_epi<EPI_DEQUANT_BIAS>(p, st);
     default: return hipErrorInvalidValue;
     }
 }
@@ -930,6 +941,7 @@ hipError_t launch_gemm(const GemmParams& p, int epi, hipStream_t st)
     if (p.a_frag == 1 && !gemm_takes_skinny(p, epi)) return hipErrorInvalidValue; // (only the skinny kernel reads that image)
     if (p.a_frag == 2 && !(epi == EPI_DEQUANT && gemm_tp_fused_supported(p.M, p.N, p.K, p.O))) return hipErrorInvalidValue;
     if (p.a_frag < 0 || p.a_frag > 2) return hipErrorInvalidValue;
+    if (epi == EPI_DEQUANT_BIAS && (p.bias == nullptr || p.Y != nullptr)) return hipErrorInvalidValue; // (no bias form with an addend)
     const int variant = gemm_variant();
     auto chose = [](const char* name) { g_last_kernel.store(name, std::memory_order_relaxed); };
     // M <= 16, and M <= 32 on narrow outputs: the weight-streaming GEMV-like kernel (measured against the split-K tiles)
@@ -968,6 +980,7 @@ hipError_t launch_gemm(const GemmParams& p, int epi, hipStream_t st)
     case EPI_DEQUANT: return launch_epi<EPI_DEQUANT>(p, st);
     case EPI_DEQUANT_SILU: return launch_epi<EPI_DEQUANT_SILU>(p, st);
     case EPI_DEQUANT_SILU_MUL: return launch_epi<EPI_DEQUANT_SILU_MUL>(p, st);
+    case EPI_DEQUANT_BIAS: return launch_epi<EPI_DEQUANT_BIAS>(p, st);
     default: return launch_epi<EPI_INT32>(p, st);
     }
 }

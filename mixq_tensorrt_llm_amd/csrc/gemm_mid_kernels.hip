@@ -65,7 +65,7 @@ struct Layout {
 template <int KEEP>
 struct MidEpiPre {
     float sa[KEEP];
-    uint2 sw[KEEP][2], y[KEEP][2];
+    uint2 sw[KEEP][2], y[KEEP][2], bias[KEEP][2]; // (bias: EPI_DEQUANT_BIAS only)
 };
 
 // half tile h of a wave tile (order: n tile i, m tile j, half gh): rows m_of(h), first column n_of(h) of this lane's quads g2 = 0, 1 (+ 8 g2)
@@ -92,6 +92,7 @@ __device__ __forceinline__ void mid_epi_prefetch(MidEpiPre<L::KEEP>& e, const Ge
         for (int g2 = 0; g2 < 2; ++g2) {
             const int nb = min(t.n(n0, wn, lh) + 8 * g2, p.N - 4);
             e.sw[k][g2] = *reinterpret_cast<const uint2*>(p.sW + nb);
+            if constexpr (EPI == EPI_DEQUANT_BIAS) e.bias[k][g2] = *reinterpret_cast<const uint2*>(p.bias + nb);
             e.y[k][g2] = p.Y != nullptr ? *reinterpret_cast<const uint2*>(p.Y + (int64_t)mp * p.N + nb) : make_uint2(0u, 0u);
         }
     }
@@ -272,6 +273,13 @@ __device__ __forceinline__ void mid_finish(const GemmParams& p, char* smem, v16i
                                                 (uint16_t)(mb.y >> 16)};
 #pragma unroll
                         for (int e = 0; e < 4; ++e) oh[e] = f2h_bits(h2f(oh[e]) * h2f(mh[e]));
+                    }
+                    if constexpr (EPI == EPI_DEQUANT_BIAS) { // the layer's bias: one fp16 add of the rounded result
+                        const uint2 bb = pre.bias[k][g2];
+                        const uint16_t bh[4] = {(uint16_t)(bb.x & 0xffffu), (uint16_t)(bb.x >> 16), (uint16_t)(bb.y & 0xffffu),
+                                                (uint16_t)(bb.y >> 16)};
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) oh[e] = hadd_bits(oh[e], bh[e]);
                     }
                     uint2 o;
                     o.x = (unsigned)oh[0] | ((unsigned)oh[1] << 16);
@@ -544,6 +552,7 @@ hipError_t launch_gemm_mid(const GemmParams& p, int epi, hipStream_t st)
     case EPI_DEQUANT: return launch_mid_epi<EPI_DEQUANT>(p, st);
     case EPI_DEQUANT_SILU: return launch_mid_epi<EPI_DEQUANT_SILU>(p, st);
     case EPI_DEQUANT_SILU_MUL: return launch_mid_epi<EPI_DEQUANT_SILU_MUL>(p, st);
+    case EPI_DEQUANT_BIAS: return launch_mid_epi<EPI_DEQUANT_BIAS>(p, st);
     default: return launch_mid_epi<EPI_INT32>(p, st);
     }
 }

@@ -316,6 +316,14 @@ __global__ __launch_bounds__(512) void gemm_w8a8o16_pp128_kernel(const GemmParam
         for (int g = 0; g < 4; ++g)
             swq[i][g] = EPI == EPI_F16GEMM ? make_uint2(0u, 0u)
                                            : *reinterpret_cast<const uint2*>(p.sW + min(n0 + wn * 64 + i * 32 + 4 * lh + 8 * g, p.N - 4));
+    uint2 bq[2][4]; // (EPI_DEQUANT_BIAS) the layer's bias of the same column quads, requested with the weight scales
+    if constexpr (EPI == EPI_DEQUANT_BIAS) {
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int g = 0; g < 4; ++g)
+                bq[i][g] = *reinterpret_cast<const uint2*>(p.bias + min(n0 + wn * 64 + i * 32 + 4 * lh + 8 * g, p.N - 4));
+    }
     constexpr bool HAS_MUL = EPI == EPI_DEQUANT_SILU_MUL;
     uint2 yq[2][4], mq[2][4];
     uint4 ypre[4], mpre[4];
@@ -388,6 +396,7 @@ __global__ __launch_bounds__(512) void gemm_w8a8o16_pp128_kernel(const GemmParam
                 }
                 v2h o16 = f2h2_of_f32_results(v0, v1);
                 if (EPI == EPI_DEQUANT_SILU_MUL) o16 = o16 * __builtin_bit_cast(v2h, e2 ? mulq.y : mulq.x); // gate * up
+                if constexpr (EPI == EPI_DEQUANT_BIAS) o16 = o16 + __builtin_bit_cast(v2h, e2 ? bq[i][g].y : bq[i][g].x); // + bias (fp16 add)
                 __builtin_memcpy(&ow[e2 >> 1], &o16, 4);
             }
             const int c = i * 4 + g; // 16-byte chunk of the 128-byte row
@@ -454,7 +463,9 @@ template <int EPI>
 static hipError_t launch_pp128_epi(const GemmParams& p, hipStream_t st)
 {
     if (p.O > 0) return launch_pp128_cfg<EPI, true, false>(p, st); // the API never passes both an addend and outliers
-    if (p.Y != nullptr) return launch_pp128_cfg<EPI, false, true>(p, st);
+    if constexpr (EPI == EPI_DEQUANT_BIAS) {
+        if (p.Y != nullptr) return hipErrorInvalidValue; // (the bias epilogue takes no addend)
+    } else if (p.Y != nullptr) return launch_pp128_cfg<EPI, false, true>(p, st);
     return launch_pp128_cfg<EPI, false, false>(p, st);
 }
 
@@ -474,6 +485,7 @@ hipError_t launch_gemm_pp128(const GemmParams& p, int epi, hipStream_t st)
     case EPI_DEQUANT: return launch_pp128_epi<EPI_DEQUANT>(p, st);
     case EPI_DEQUANT_SILU: return launch_pp128_epi<EPI_DEQUANT_SILU>(p, st);
     case EPI_DEQUANT_SILU_MUL: return launch_pp128_epi<EPI_DEQUANT_SILU_MUL>(p, st);
+    case EPI_DEQUANT_BIAS: return launch_pp128_epi<EPI_DEQUANT_BIAS>(p, st);
     default: return launch_pp128_cfg<EPI_INT32, false, false>(p, st);
     }
 }

@@ -99,14 +99,16 @@ __device__ __forceinline__ void wait_vmcnt()
 //   * The last arriver, after finishing its own share, finishes every DEFERRED share too: all S partial sums of such a
 //     share are in the scratch by then.  Every share is finished exactly once, by its owner or by the last arriver.
 // The last workgroup of a group to be done with the words re-arms them for the next launch.
-// TP = true (EPI_DEQUANT, no K split): the store path writes every finished block into this rank's column block of ALL
+// TP = true (EPI_DEQUANT or EPI_DEQUANT_BIAS, no K split): the store path writes every finished block into this rank's column block of ALL
 // p.tp.ndst destination buffers (row stride p.tp.ldd) with system-scope write-through stores instead of into p.D, and the
 // last tile of an M chunk to be acknowledged publishes p.tp.seq in the chunk's flag word of every destination (TpEpilogue,
 // mixq_launch.h; protocol in tp_kernels.hip).
 template <int EPI, bool HAS_O, bool HAS_Y, int ABL = 0, int SPLITK = 0, bool TP = false>
 __global__ __launch_bounds__(512) void gemm_w8a8o16_pp_kernel(const GemmParams p)
 {
-    static_assert(!TP || (SPLITK == 0 && EPI == EPI_DEQUANT && ABL == 0), "the peer-write epilogue exists for the plain kernel");
+    static_assert(!TP || (SPLITK == 0 && (EPI == EPI_DEQUANT || EPI == EPI_DEQUANT_BIAS) && ABL == 0),
+                  "the peer-write epilogue exists for the plain kernel");
+    static_assert(EPI != EPI_DEQUANT_BIAS || (!HAS_Y && ABL == 0), "the bias epilogue takes no addend y");
     constexpr int S = SPLITK ? SPLITK : 1; // workgroups per tile
     constexpr int PJ = S >= 4 ? 1 : 4 / S; // 32-row m tiles (per wave) this workgroup finishes
     constexpr int NI = S == 8 ? 1 : 2;     // 32-column n tiles (per wave) it finishes: S = 8 splits the n pair as well
@@ -604,6 +606,9 @@ __global__ __launch_bounds__(512) void gemm_w8a8o16_pp_kernel(const GemmParams p
         for (int g = 0; g < 4; ++g)
             swq[i][g] = EPI == EPI_F16GEMM ? make_uint2(0u, 0u)
                                            : *reinterpret_cast<const uint2*>(p.sW + min(n0 + wn * 64 + imap(i) * 32 + 4 * lh + 8 * g, p.N - 4));
+    // (EPI_DEQUANT_BIAS) the layer's bias is NOT held like swq: 16 more registers through the epilogue spill this kernel (it sits at
+    // 253..256 VGPRs).  dequant requests the 4 quads of its column block at its start instead (L1 / L2 hits after the first block),
+    // from an address the compiler cannot hoist out of the block loop.
     // [M,N] fp16 operands of the epilogue (the caller's addend y, the gate*up multiplicand) take the store path in
     // reverse: coalesced 16-byte loads of 128-byte row segments (8 rows per instruction), one block ahead, then through
     // the wave's window into the accumulator layout (8 bytes = 4 consecutive n of row lane & 31).  Reading them in the
@@ -643,6 +648,13 @@ __global__ __launch_bounds__(512) void gemm_w8a8o16_pp_kernel(const GemmParams p
     if (HAS_MUL) fetch(p.Mul, 0, mpre);
     // dequant of tile (i, j) with its side product P -> 4 quads (4 consecutive n of row m each) -> window
     auto dequant = [&](int i, int j, const v16f& P) __attribute__((always_inline)) {
+        uint2 bq[4];
+        if constexpr (EPI == EPI_DEQUANT_BIAS) {
+            int bcol = n0 + wn * 64 + imap(i) * 32 + 4 * lh;
+            asm volatile("" : "+v"(bcol));
+#pragma unroll
+            for (int g = 0; g < 4; ++g) bq[g] = *reinterpret_cast<const uint2*>(p.bias + min(bcol + 8 * g, p.N - 4));
+        }
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
             const uint2 swb = swq[i][g];
@@ -683,6 +695,7 @@ __global__ __launch_bounds__(512) void gemm_w8a8o16_pp_kernel(const GemmParams p
                 }
                 v2h o16 = f2h2_of_f32_results(v0, v1);
                 if (EPI == EPI_DEQUANT_SILU_MUL) o16 = o16 * __builtin_bit_cast(v2h, e2 ? mulq.y : mulq.x); // gate * up
+                if constexpr (EPI == EPI_DEQUANT_BIAS) o16 = o16 + __builtin_bit_cast(v2h, e2 ? bq[g].y : bq[g].x); // + bias (fp16 add)
                 __builtin_memcpy(&ow[e2 >> 1], &o16, 4);
             }
             if (S == 8) { // a single 32x32 tile per wave: 8-byte stores straight from the accumulator layout
@@ -866,11 +879,11 @@ int tp_flag_words(int M)
     const int tiles_m = (M + pp::BM - 1) / pp::BM, c = tp_chunk_tile_rows(M);
     return M <= 0 ? 1 : (tiles_m + c - 1) / c;
 }
-template <bool HAS_O>
+template <int EPI, bool HAS_O>
 static hipError_t launch_pp_tp_cfg(const GemmParams& p, hipStream_t st)
 {
     constexpr size_t lds = 2 * (size_t)pp::BUF + 32768;
-    auto kern = gemm_w8a8o16_pp_kernel<EPI_DEQUANT, HAS_O, false, 0, 0, true>;
+    auto kern = gemm_w8a8o16_pp_kernel<EPI, HAS_O, false, 0, 0, true>;
     static DeviceOnce once;
     if (hipError_t e = ensure_dynamic_lds(kern, lds, once); e != hipSuccess) return e;
     const int tiles = ((p.M + pp::BM - 1) / pp::BM) * ((p.N + pp::BN - 1) / pp::BN);
@@ -883,7 +896,8 @@ hipError_t launch_gemm_pp_tp(const GemmParams& p_in, hipStream_t st)
     GemmParams p = p_in;
     p.tp.chunk_tile_rows = tp_chunk_tile_rows(p.M);
     note_gemm_kernel("gemm_w8a8o16_pp_kernel<TP> (256x256 ping-pong, peer-write epilogue)");
-    return p.O > 0 ? launch_pp_tp_cfg<true>(p, st) : launch_pp_tp_cfg<false>(p, st);
+    if (p.bias != nullptr) return p.O > 0 ? launch_pp_tp_cfg<EPI_DEQUANT_BIAS, true>(p, st) : launch_pp_tp_cfg<EPI_DEQUANT_BIAS, false>(p, st);
+    return p.O > 0 ? launch_pp_tp_cfg<EPI_DEQUANT, true>(p, st) : launch_pp_tp_cfg<EPI_DEQUANT, false>(p, st);
 }
 
 template <int EPI>
@@ -891,7 +905,9 @@ static hipError_t launch_pp_epi(const GemmParams& p, hipStream_t st)
 {
     const bool has_o = p.O > 0, has_y = p.Y != nullptr;
     if (has_o) return launch_pp_cfg<EPI, true, false>(p, st); // the API never passes both an addend and outliers
-    if (has_y) return launch_pp_cfg<EPI, false, true>(p, st);
+    if constexpr (EPI == EPI_DEQUANT_BIAS) {
+        if (has_y) return hipErrorInvalidValue;
+    } else if (has_y) return launch_pp_cfg<EPI, false, true>(p, st);
     return launch_pp_cfg<EPI, false, false>(p, st);
 }
 
@@ -1035,7 +1051,9 @@ template <int EPI, int SPLITK>
 static hipError_t launch_pp_splitk_epi(const GemmParams& p, hipStream_t st)
 {
     if (p.O > 0) return launch_pp_splitk_cfg<EPI, true, false, SPLITK>(p, st);
-    if (p.Y != nullptr) return launch_pp_splitk_cfg<EPI, false, true, SPLITK>(p, st);
+    if constexpr (EPI == EPI_DEQUANT_BIAS) {
+        if (p.Y != nullptr) return hipErrorInvalidValue;
+    } else if (p.Y != nullptr) return launch_pp_splitk_cfg<EPI, false, true, SPLITK>(p, st);
     return launch_pp_splitk_cfg<EPI, false, false, SPLITK>(p, st);
 }
 
@@ -1060,6 +1078,10 @@ hipError_t launch_gemm_pp_splitk(const GemmParams& p_in, int epi, hipStream_t st
         return s == 8   ? launch_pp_splitk_epi<EPI_DEQUANT_SILU_MUL, 8>(p, st)
                : s == 4 ? launch_pp_splitk_epi<EPI_DEQUANT_SILU_MUL, 4>(p, st)
                         : launch_pp_splitk_epi<EPI_DEQUANT_SILU_MUL, 2>(p, st);
+    case EPI_DEQUANT_BIAS:
+        return s == 8   ? launch_pp_splitk_epi<EPI_DEQUANT_BIAS, 8>(p, st)
+               : s == 4 ? launch_pp_splitk_epi<EPI_DEQUANT_BIAS, 4>(p, st)
+                        : launch_pp_splitk_epi<EPI_DEQUANT_BIAS, 2>(p, st);
     default: return hipErrorInvalidValue;
     }
 }
@@ -1091,6 +1113,7 @@ hipError_t launch_gemm_pp(const GemmParams& p, int epi, hipStream_t st)
     case EPI_DEQUANT: return launch_pp_epi<EPI_DEQUANT>(p, st);
     case EPI_DEQUANT_SILU: return launch_pp_epi<EPI_DEQUANT_SILU>(p, st);
     case EPI_DEQUANT_SILU_MUL: return launch_pp_epi<EPI_DEQUANT_SILU_MUL>(p, st);
+    case EPI_DEQUANT_BIAS: return launch_pp_epi<EPI_DEQUANT_BIAS>(p, st);
     default: return launch_pp_cfg<EPI_INT32, false, false>(p, st);
     }
 }

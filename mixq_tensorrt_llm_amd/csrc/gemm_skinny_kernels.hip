@@ -295,6 +295,15 @@ __global__ __launch_bounds__(KW * 64) void gemm_skinny_kernel(const GemmParams p
 #pragma unroll
                 for (int e = 0; e < 4; ++e) oh[e] = f2h_bits(h2f(oh[e]) * h2f(mh[e]));
             }
+            if constexpr (EPI == EPI_DEQUANT_BIAS) { // the layer's bias: one fp16 add of the rounded result
+                // (requested here, not with psw at kernel start: two registers more through the main loop cost the 17..32-row forms
+                //  half their occupancy -- 240 + 16 -> 242 + 16 of 256 registers)
+                const uint2 bb = *reinterpret_cast<const uint2*>(p.bias + nb);
+                const uint16_t bh[4] = {(uint16_t)(bb.x & 0xffffu), (uint16_t)(bb.x >> 16), (uint16_t)(bb.y & 0xffffu),
+                                        (uint16_t)(bb.y >> 16)};
+#pragma unroll
+                for (int e = 0; e < 4; ++e) oh[e] = hadd_bits(oh[e], bh[e]);
+            }
             uint2 o;
             o.x = (unsigned)oh[0] | ((unsigned)oh[1] << 16);
             o.y = (unsigned)oh[2] | ((unsigned)oh[3] << 16);
@@ -704,6 +713,7 @@ hipError_t launch_gemm_skinny(const GemmParams& p, int epi, hipStream_t st)
     case EPI_DEQUANT: return launch_skinny_epi<EPI_DEQUANT>(p, st);
     case EPI_DEQUANT_SILU: return launch_skinny_epi<EPI_DEQUANT_SILU>(p, st);
     case EPI_DEQUANT_SILU_MUL: return launch_skinny_epi<EPI_DEQUANT_SILU_MUL>(p, st);
+    case EPI_DEQUANT_BIAS: return launch_skinny_epi<EPI_DEQUANT_BIAS>(p, st);
     default: return launch_skinny_epi<EPI_INT32>(p, st);
     }
 }

@@ -678,7 +678,7 @@ int mixq_gemm_mixed(const int8_t* qA, const int8_t* W, const void* sA, const voi
 
 static int gemm_mixed_impl(const int8_t* qA, const int8_t* W, const void* sA, const void* sW, const void* fpA, const void* fpW,
                            void* Out, int M, int N, int K, int O, void* scratch, size_t scratch_bytes, void* stream,
-                           int a_frag, const void* b_image = nullptr, bool image_resolved = false);
+                           int a_frag, const void* b_image = nullptr, bool image_resolved = false, const void* bias = nullptr);
 
 int mixq_gemm_mixed_scratch(const int8_t* qA, const int8_t* W, const void* sA, const void* sW, const void* fpA,
                             const void* fpW, void* Out, int M, int N, int K, int O, void* scratch, size_t scratch_bytes,
@@ -687,12 +687,22 @@ int mixq_gemm_mixed_scratch(const int8_t* qA, const int8_t* W, const void* sA, c
     return gemm_mixed_impl(qA, W, sA, sW, fpA, fpW, Out, M, N, K, O, scratch, scratch_bytes, stream, 0);
 }
 
+int mixq_gemm_mixed_bias(const int8_t* qA, const int8_t* W, const void* sA, const void* sW, const void* fpA, const void* fpW,
+                         const void* bias, void* Out, int M, int N, int K, int O, void* scratch, size_t scratch_bytes, void* stream)
+{
+    if (!bias) return MIXQ_E_BADARG;
+    if (!aligned16(bias)) return MIXQ_E_ALIGN;
+    if (O > kNumOutliers) return MIXQ_E_SHAPE; // (the two-step order of more outlier columns feeds an addend; the bias form takes none)
+    return gemm_mixed_impl(qA, W, sA, sW, fpA, fpW, Out, M, N, K, O, scratch, scratch_bytes, stream, 0, nullptr, false, bias);
+}
+
 // a_frag: layout of qA (GemmParams::a_frag): enqueue's own quantiser may write the consuming kernel's preferred image; the
 // public entries take row-major qA
 // b_image / image_resolved: the caller has already looked the weight's image up for this call (one lookup per call)
+// bias: the layer's fp16 [N] bias (EPI_DEQUANT_BIAS: the same kernel as EPI_DEQUANT, one fp16 add in its epilogue), or null
 static int gemm_mixed_impl(const int8_t* qA, const int8_t* W, const void* sA, const void* sW, const void* fpA, const void* fpW,
                            void* Out, int M, int N, int K, int O, void* scratch, size_t scratch_bytes, void* stream,
-                           int a_frag, const void* b_image, bool image_resolved)
+                           int a_frag, const void* b_image, bool image_resolved, const void* bias)
 {
     if (M < 0 || N < 0 || K <= 0 || O < 0) return MIXQ_E_BADARG;
     if (M == 0 || N == 0) return MIXQ_OK;
@@ -714,8 +724,10 @@ static int gemm_mixed_impl(const int8_t* qA, const int8_t* W, const void* sA, co
     if (scratch && aligned16(scratch) && scratch_bytes >= gemm_scratch_bytes(M, N, K)) p.splitk_ws = scratch;
     if (O <= kNumOutliers) {
         p.fpA = static_cast<const uint16_t*>(fpA), p.fpW = static_cast<const uint16_t*>(fpW), p.O = O;
-        return hip_rc(mixq::launch_gemm(p, mixq::EPI_DEQUANT, st));
+        p.bias = static_cast<const uint16_t*>(bias);
+        return hip_rc(mixq::launch_gemm(p, bias ? mixq::EPI_DEQUANT_BIAS : mixq::EPI_DEQUANT, st));
     }
+    if (bias) return MIXQ_E_SHAPE;
     // more outlier columns than one LDS pass holds: the reference's own two-step order (side GEMM into Out, then C = D = Out)
     hipError_t e = mixq::launch_gemm_fp16(fpA, fpW, Out, M, N, O, st);
     if (e != hipSuccess) return MIXQ_E_HIP;
@@ -944,7 +956,8 @@ static int enqueue_qa_frag(int64_t M, int64_t N, int64_t K, void* scratch, const
 }
 
 static int enqueue_impl(const mixq_handle* h, const mixq_tensor_desc* inputDesc, const void* const* inputs,
-                        void* const* outputs, void* workspace, void* stream, void* ev_gemm_start, void* ev_gemm_stop)
+                        void* const* outputs, void* workspace, void* stream, void* ev_gemm_start, void* ev_gemm_stop,
+                        const void* bias = nullptr)
 {
     if (!h || !inputDesc || !inputs || !outputs) return MIXQ_E_BADARG;
     const mixq_tensor_desc& a = inputDesc[0];
@@ -992,6 +1005,8 @@ static int enqueue_impl(const mixq_handle* h, const mixq_tensor_desc* inputDesc,
         }
         if (K % 8) return MIXQ_E_SHAPE;
         if (!aligned16(A)) return MIXQ_E_ALIGN;
+        if (bias && (K % 16 || N % 16)) return MIXQ_E_SHAPE; // (what the GEMM stage checks, before the quantiser runs)
+        if (bias && (!aligned16(W) || !aligned16(Out) || !aligned16(scale_b) || !aligned16(fp_weight))) return MIXQ_E_ALIGN;
         // decode batches that the weight-streaming skinny GEMM serves: the quantiser writes qA in that kernel's MFMA fragment
         // order, so that each of its qA loads is one contiguous 1-KiB read (profiles/r03_small_m_timeline.txt)
         // (Large calls keep the row-major image: a K-slice-major one -- 8 consecutive rows of a 128-byte slice contiguous, one LDS-DMA
@@ -1004,11 +1019,19 @@ static int enqueue_impl(const mixq_handle* h, const mixq_tensor_desc* inputDesc,
         if (rc != MIXQ_OK) return rc;
         if (ev_gemm_start && hipEventRecord(static_cast<hipEvent_t>(ev_gemm_start), st) != hipSuccess) return MIXQ_E_HIP;
         rc = gemm_mixed_impl(qA, W, sA, scale_b, fpA, fp_weight, Out, (int)M, (int)N, (int)K, kNumOutliers, scratch,
-                             scratch_bytes, stream, frag, img, true);
+                             scratch_bytes, stream, frag, img, true, bias);
         if (ev_gemm_stop && hipEventRecord(static_cast<hipEvent_t>(ev_gemm_stop), st) != hipSuccess) return MIXQ_E_HIP;
         return rc;
     }
-    return mixq_w8a16_gemm_forward(A, q_weight, scaling_factors, Out, (int)M, (int)N, (int)K, stream);
+    if (!bias) return mixq_w8a16_gemm_forward(A, q_weight, scaling_factors, Out, (int)M, (int)N, (int)K, stream);
+    // M <= 4 with the bias: the same two forms mixq_w8a16_gemm_forward picks from (the GEMV / the fpA_intB skinny form)
+    if (K % 64 || N % 2) return MIXQ_E_SHAPE;
+    if (!aligned16(A) || !aligned16(q_weight)) return MIXQ_E_ALIGN;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (!mixq::w8a16_skinny_takes((int)M, (int)N, (int)K))
+        return hip_rc(mixq::launch_w8a16(A, q_weight, scaling_factors, Out, (int)M, (int)N, (int)K, st, bias));
+    if (K % 8 || (reinterpret_cast<uintptr_t>(Out) & 3u)) return MIXQ_E_ALIGN;
+    return hip_rc(mixq::launch_w8a16_skinny_bias(A, q_weight, scaling_factors, Out, (int)M, (int)N, (int)K, bias, st));
 }
 
 // What mixq_enqueue would launch for a call with M rows on an [N, K] layer, as text (host only, no GPU needed; include/mixq.h).
@@ -1039,6 +1062,13 @@ int mixq_enqueue(const mixq_handle* h, const mixq_tensor_desc* inputDesc, const 
     return enqueue_impl(h, inputDesc, inputs, outputs, workspace, stream, nullptr, nullptr);
 }
 
+int mixq_enqueue_bias(const mixq_handle* h, const mixq_tensor_desc* inputDesc, const mixq_tensor_desc* /*outputDesc*/,
+                      const void* const* inputs, void* const* outputs, const void* bias_f16, void* workspace, void* stream)
+{
+    if (bias_f16 && !aligned16(bias_f16)) return MIXQ_E_ALIGN;
+    return enqueue_impl(h, inputDesc, inputs, outputs, workspace, stream, nullptr, nullptr, bias_f16);
+}
+
 int mixq_enqueue_profiled(const mixq_handle* h, const mixq_tensor_desc* inputDesc,
                           const mixq_tensor_desc* /*outputDesc*/, const void* const* inputs, void* const* outputs,
                           void* workspace, void* stream, void* ev_gemm_start, void* ev_gemm_stop)
@@ -1055,8 +1085,8 @@ int mixq_tp_fused_supported(int64_t M, int64_t N_local, int64_t K)
 
 int mixq_tp_flag_words(int64_t M) { return M > 0 && M <= INT32_MAX ? mixq::tp_flag_words((int)M) : 1; }
 
-int mixq_enqueue_tp(const mixq_handle* h, const mixq_tensor_desc* inputDesc, const void* const* inputs, void* workspace,
-                    const mixq_tp_epilogue* tp, void* stream)
+static int enqueue_tp_impl(const mixq_handle* h, const mixq_tensor_desc* inputDesc, const void* const* inputs, const void* bias,
+                           void* workspace, const mixq_tp_epilogue* tp, void* stream)
 {
     if (!h || !inputDesc || !inputs || !tp) return MIXQ_E_BADARG;
     const mixq_tensor_desc& a = inputDesc[0];
@@ -1074,6 +1104,7 @@ int mixq_enqueue_tp(const mixq_handle* h, const mixq_tensor_desc* inputDesc, con
         if (!inputs[i]) return MIXQ_E_BADARG;
     if (!workspace) return MIXQ_E_WORKSPACE;
     if (!aligned16(inputs[0]) || !aligned16(inputs[1]) || !aligned16(inputs[2]) || !aligned16(inputs[3])) return MIXQ_E_ALIGN;
+    if (bias && !aligned16(bias)) return MIXQ_E_ALIGN;
     uintptr_t base = align_up(reinterpret_cast<uintptr_t>(workspace), kWorkspaceAlign);
     int8_t* qA = reinterpret_cast<int8_t*>(base);
     base = align_up(base + (size_t)M * (size_t)K, kWorkspaceAlign);
@@ -1086,6 +1117,7 @@ int mixq_enqueue_tp(const mixq_handle* h, const mixq_tensor_desc* inputDesc, con
     p.sA = static_cast<const uint16_t*>(sA), p.sW = static_cast<const uint16_t*>(inputs[2]);
     p.fpA = static_cast<const uint16_t*>(fpA), p.fpW = static_cast<const uint16_t*>(inputs[3]);
     p.O = kNumOutliers, p.M = (int)M, p.N = (int)N, p.K = (int)K;
+    p.bias = static_cast<const uint16_t*>(bias); // (this rank's [N] slice; launch_gemm_pp_tp takes the bias epilogue when set)
     p.zeros = mixq::zero_page();
     if (!p.zeros) return MIXQ_E_HIP;
     p.tp.ndst = tp->ndst, p.tp.ldd = tp->n_total, p.tp.seq = tp->seq;
@@ -1099,6 +1131,18 @@ int mixq_enqueue_tp(const mixq_handle* h, const mixq_tensor_desc* inputDesc, con
                                                (int)M, (int)K, kNumOutliers, false, st, nullptr));
     if (rc != MIXQ_OK) return rc;
     return hip_rc(mixq::launch_gemm_pp_tp(p, st));
+}
+
+int mixq_enqueue_tp(const mixq_handle* h, const mixq_tensor_desc* inputDesc, const void* const* inputs, void* workspace,
+                    const mixq_tp_epilogue* tp, void* stream)
+{
+    return enqueue_tp_impl(h, inputDesc, inputs, nullptr, workspace, tp, stream);
+}
+
+int mixq_enqueue_tp_bias(const mixq_handle* h, const mixq_tensor_desc* inputDesc, const void* const* inputs, const void* bias_f16,
+                         void* workspace, const mixq_tp_epilogue* tp, void* stream)
+{
+    return enqueue_tp_impl(h, inputDesc, inputs, bias_f16, workspace, tp, stream);
 }
 
 

@@ -47,6 +47,10 @@ __device__ __forceinline__ uint16_t f2h_bits(float f)
     return b;
 }
 
+// fp16 + fp16, rounded once (EPI_DEQUANT_BIAS): the fp32 sum rounded to fp16 is the correctly rounded fp16 sum (__hadd,
+// torch's fp16 add) -- fp32 carries more than 2 x 11 + 2 bits, so the double rounding is innocuous.
+__device__ __forceinline__ uint16_t hadd_bits(uint16_t a, uint16_t b) { return f2h_bits(h2f(a) + h2f(b)); }
+
 // SiLU as the reference writes it (linear_combination_dequant.h:167-170, cult.cu:2301-2304): x / (1 + expf(-x)) with the
 // accurate library expf (<= 1 ulp, like CUDA's expf without -use_fast_math) and an IEEE division -- not the
 // hardware v_exp_f32 approximation (__expf).

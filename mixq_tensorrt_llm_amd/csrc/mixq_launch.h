@@ -36,8 +36,10 @@ inline hipError_t ensure_dynamic_lds(Kern kern, size_t bytes, DeviceOnce& once)
 int num_cus(); // of the current device (cached per device)
 
 enum { EPI_DEQUANT = 0, EPI_DEQUANT_SILU = 1, EPI_INT32 = 2, EPI_DEQUANT_SILU_MUL = 3,
-       EPI_F16GEMM = 4 }; // 4: the operands are fp16 (K counts BYTES), fp32 accumulation, D = fp16(A B^T): the ping-pong kernel
+       EPI_F16GEMM = 4,   // 4: the operands are fp16 (K counts BYTES), fp32 accumulation, D = fp16(A B^T): the ping-pong kernel
                           // with v_mfma_f32_32x32x16_f16 (second pass of the two-pass fpA_intB GEMM, w8a16_gemm_kernels.hip)
+       EPI_DEQUANT_BIAS = 5 }; // 5: EPI_DEQUANT, then D = fp16(D + bias[n]) on the rounded value (GemmParams::bias, the layer's fp16 [N]
+                               // bias; the reference adds it after the plugin, plugin.py:158-160).  Kernel choice: the same as EPI_DEQUANT
 constexpr bool epi_has_silu(int epi) { return epi == EPI_DEQUANT_SILU || epi == EPI_DEQUANT_SILU_MUL; }
 
 // TP all-gather fused into the GEMM's store path (gemm_pp_kernels.hip, TP = true): every finished 32-row block of a wave
@@ -88,6 +90,7 @@ struct GemmParams {
     void* splitk_ws;      // device scratch of gemm_splitk_workspace_size bytes whose arrival words are zero, or null: lets
                           // launch_gemm split K over 2 / 4 workgroups per 256x256 tile when the tiles alone cover at
                           // most half / a quarter of the CUs (gemm_pp_kernels.hip)
+    const uint16_t* bias; // fp16 [N] of EPI_DEQUANT_BIAS (added once, by whoever runs the final epilogue of an element), else null
 };
 
 hipError_t launch_gemm(const GemmParams& p, int epi, hipStream_t st);
@@ -96,7 +99,7 @@ int gemm_deep_factor(int M, int N, int K, bool have_scratch);                 //
 int skinny_weight_route(int a_frag, bool image, int M, int N, int K);         // GemmParams::b_frag the skinny launcher would set
 hipError_t launch_gemm_pp(const GemmParams& p, int epi, hipStream_t st);  // 256x256 ping-pong schedule
 hipError_t launch_gemm_pp128(const GemmParams& p, int epi, hipStream_t st);
-hipError_t launch_gemm_pp_tp(const GemmParams& p, hipStream_t st); // EPI_DEQUANT with p.tp.ndst destinations instead of p.D
+hipError_t launch_gemm_pp_tp(const GemmParams& p, hipStream_t st); // EPI_DEQUANT (EPI_DEQUANT_BIAS when p.bias) with p.tp.ndst destinations instead of p.D
 // D[M,N] fp16 = A[M,K] B[N,K]^T, fp16 operands (K % 8 == 0, N % 8 == 0, 16-byte aligned rows), fp32 accumulation
 hipError_t launch_gemm_f16_pp(const void* A, const void* B, void* D, int M, int N, int K, const void* zeros, hipStream_t st);
 hipError_t launch_gemm_f16_pp128(const void* A, const void* B, void* D, int M, int N, int K, const void* zeros, hipStream_t st); // 128 x 256 tiles // 128x256 ping-pong schedule (mid-size problems)
@@ -133,6 +136,9 @@ hipError_t launch_gemm_skinny(const GemmParams& p, int epi, hipStream_t st); // 
 hipError_t launch_gemm_pp_ablate(const GemmParams& p, int abl, hipStream_t st);  // timing experiments only
 void set_gemm_variant(int v);
 bool w8a16_skinny_takes(int M, int N, int K); // the fpA_intB skinny form serves this shape (w8a16_gemm_kernels.hip)
+// the same form with the layer's fp16 [N] bias added to the rounded result (M <= 16, w8a16_skinny_takes only)
+hipError_t launch_w8a16_skinny_bias(const void* A, const uint8_t* Wq, const void* scale, void* Out, int M, int N, int K,
+                                    const void* bias, hipStream_t st);
 // fpA_intB measurement / test knobs (mixq_debug_set_gemm_variant 80..89, 831..834, 840..844, 850..858, 800 + ABL); `form`:
 //   -1 everything automatic | 0 narrow form | 1..4 wide form with 32 / 64 / 128 / 256-row tiles | 100 + ABL ablation of the
 //   256-row form | 200 / 201 / 202 two-pass form automatic / never / always, 203 / 204 its second pass on 256- / 128-row tiles
@@ -194,7 +200,7 @@ hipError_t launch_gemm_skinny_s4q(const GemmParams& p, int epi, hipStream_t st);
 hipError_t launch_unpack_s4_columns(const uint8_t* weight, const int32_t* ind, int rows, int cols_packed, int n,
                                     void* out, hipStream_t st);
 hipError_t launch_w8a16(const void* A, const uint8_t* Wq, const void* scale, void* Out, int M, int N, int K,
-                        hipStream_t st);
+                        hipStream_t st, const void* bias = nullptr); // bias: fp16 [N] added to the rounded result, or null
 
 void note_gemm_kernel(const char* name);
 // TP all-gather of the output columns as one-sided peer writes + flags (tp_kernels.hip)

@@ -722,10 +722,13 @@ typedef float v4f_ __attribute__((ext_vector_type(4)));
 // model with layers that large streams them from HBM once per step whatever the policy.  The int8 decode-batch GEMM measured +2 %
 // with the same hint on the row-major weight and keeps plain loads THERE; its registered weight images of 32 MiB and more (WFRAG == 2,
 // gemm_skinny_kernels.hip) and the packed-int4 stream (int4_gemm_kernels.hip) do use non-temporal loads.
-template <int MT, int KW, int CG, bool NTW = false>
+// BIAS: Out = fp16(fp16(sum) + bias[n]) -- the layer's fp16 [N] bias added to the rounded result, requested behind the main loop
+// (requested with the scales, its registers through the loop cost 7 -> 4 waves per SIMD).
+template <int MT, int KW, int CG, bool NTW = false, bool BIAS = false>
 __global__ __launch_bounds__(KW * 64) void w8a16_skinny_kernel(const uint16_t* __restrict__ A, const uint8_t* __restrict__ Wq,
                                                                 const uint16_t* __restrict__ scale,
-                                                                uint16_t* __restrict__ Out, int M, int N, int K)
+                                                                uint16_t* __restrict__ Out, int M, int N, int K,
+                                                                const uint16_t* __restrict__ bias)
 {
     __shared__ v4f_ part[KW][CG][MT][64]; // [K part][column group][token tile][lane]
     const int lane = threadIdx.x & 63;
@@ -812,7 +815,14 @@ __global__ __launch_bounds__(KW * 64) void w8a16_skinny_kernel(const uint16_t* _
         const int m = t * 16 + ln, n = n0 + cg * 16 + 4 * kq;
         if (m >= M) continue;
         uint16_t* dst = Out + (int64_t)m * N + n;
-        const v2h lo = f2h2(sum[0], sum[1]), hi = f2h2(sum[2], sum[3]);
+        v2h lo = f2h2(sum[0], sum[1]), hi = f2h2(sum[2], sum[3]);
+        if constexpr (BIAS) { // the layer's bias: one fp16 add of the rounded result (columns n .. n + 3, clamped; past N never stored)
+            unsigned bw[2];
+#pragma unroll
+            for (int r2 = 0; r2 < 2; ++r2)
+                bw[r2] = (unsigned)bias[min(n + 2 * r2, N - 1)] | ((unsigned)bias[min(n + 2 * r2 + 1, N - 1)] << 16);
+            lo = lo + __builtin_bit_cast(v2h, bw[0]), hi = hi + __builtin_bit_cast(v2h, bw[1]);
+        }
         if (n + 3 < N && (N & 3) == 0) {
             *reinterpret_cast<uint2*>(dst) = uint2{__builtin_bit_cast(unsigned, lo), __builtin_bit_cast(unsigned, hi)};
         } else {
@@ -1098,19 +1108,39 @@ static hipError_t launch_wo(const uint16_t* A, const uint8_t* Wq, const uint16_t
     return hipGetLastError();
 }
 
-template <int MT, int KW, int CG>
+template <int MT, int KW, int CG, bool BIAS = false>
 static hipError_t launch_wo_skinny(const uint16_t* A, const uint8_t* Wq, const uint16_t* scale, uint16_t* Out, int M, int N,
-                                   int K, hipStream_t st)
+                                   int K, hipStream_t st, const uint16_t* bias = nullptr)
 {
     const dim3 grid((unsigned)((N + 16 * CG - 1) / (16 * CG))), block(KW * 64);
     if constexpr (MT == 1) { // (decode and the smallest decode batches: the forms a model's decode step runs)
         if (g_wo_nt.load() != 0 && (int64_t)N * K >= wo_nt_weight_bytes()) {
-            hipLaunchKernelGGL((w8a16_skinny_kernel<MT, KW, CG, true>), grid, block, 0, st, A, Wq, scale, Out, M, N, K);
+            hipLaunchKernelGGL((w8a16_skinny_kernel<MT, KW, CG, true, BIAS>), grid, block, 0, st, A, Wq, scale, Out, M, N, K, bias);
             return hipGetLastError();
         }
     }
-    hipLaunchKernelGGL((w8a16_skinny_kernel<MT, KW, CG>), grid, block, 0, st, A, Wq, scale, Out, M, N, K);
+    hipLaunchKernelGGL((w8a16_skinny_kernel<MT, KW, CG, false, BIAS>), grid, block, 0, st, A, Wq, scale, Out, M, N, K, bias);
     return hipGetLastError();
+}
+
+// M <= 4 rows with the layer's bias (mixq_enqueue_bias): the skinny form wherever w8a16_skinny_takes (same pick as without it)
+hipError_t launch_w8a16_skinny_bias(const void* A, const uint8_t* Wq, const void* scale, void* Out, int M, int N, int K,
+                                    const void* bias, hipStream_t st)
+{
+    const int pick = wo_skinny_pick(M, N, K);
+    if (pick == 0 || M > 16 || bias == nullptr) return hipErrorInvalidValue;
+    const uint16_t* a = static_cast<const uint16_t*>(A);
+    const uint16_t* s = static_cast<const uint16_t*>(scale);
+    const uint16_t* b = static_cast<const uint16_t*>(bias);
+    uint16_t* o = static_cast<uint16_t*>(Out);
+    switch (pick) {
+    case 2: return launch_wo_skinny<1, 8, 2, true>(a, Wq, s, o, M, N, K, st, b);
+    case 3: return launch_wo_skinny<1, 16, 2, true>(a, Wq, s, o, M, N, K, st, b);
+    case 4: return launch_wo_skinny<1, 8, 4, true>(a, Wq, s, o, M, N, K, st, b);
+    case 6: return launch_wo_skinny<1, 8, 1, true>(a, Wq, s, o, M, N, K, st, b);
+    case 7: return launch_wo_skinny<1, 16, 1, true>(a, Wq, s, o, M, N, K, st, b);
+    default: return launch_wo_skinny<1, 16, 4, true>(a, Wq, s, o, M, N, K, st, b);
+    }
 }
 
 template <int MTW, int WMH, int NST, int ABL = 0, bool RW = false>

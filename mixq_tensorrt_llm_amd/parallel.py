@@ -260,12 +260,13 @@ class PeerGather:
             self._wait(par, 1, st)
         return self._view(par, m)
 
-    def enqueue_gather(self, plug, inputs, workspace=None):
+    def enqueue_gather(self, plug, inputs, workspace=None, bias=None):
         """The operator AND its all-gather in one pass (``mixq_enqueue_tp``): the GEMM's store path writes this rank's
         column block straight into every rank's buffer, chunk flags are published as the M chunks retire -- no
         [m, N/tp] output, no push launch, no second read.  ``plug``: plugin.MixQPlugin of the shard; ``inputs``: the 7
         carriers of ``MixQPlugin.enqueue``.  Returns the gathered fp16 [m, N] view, or None when the shape does not take
-        the 256 x 256 ping-pong kernel (caller: ``plug.enqueue`` + ``gather``)."""
+        the 256 x 256 ping-pong kernel (caller: ``plug.enqueue`` + ``gather``).  ``bias``: this rank's [N/tp] slice of
+        the layer's bias, added before the columns are written (``mixq_enqueue_tp_bias``), or None."""
         from . import _lib
         A = inputs[0]
         K = A.shape[-1]
@@ -277,10 +278,15 @@ class PeerGather:
         in_ptrs = (ctypes.c_void_p * 7)(*[t.data_ptr() for t in inputs])
         if workspace is None:
             workspace = plug._workspace(A.device, plug.workspace_size(max(m, 1), self.n_loc, K))
-        return self.enqueue_gather_raw(plug._h, in_desc, in_ptrs, ctypes.c_void_p(workspace.data_ptr()), m, K)
+        if bias is not None:
+            from .plugin import fp16_bias
+            bias = fp16_bias(bias, self.n_loc, A.device)
+        return self.enqueue_gather_raw(plug._h, in_desc, in_ptrs, ctypes.c_void_p(workspace.data_ptr()), m, K,
+                                       bias_ptr=bias.data_ptr() if bias is not None else None)
 
-    def enqueue_gather_raw(self, handle, in_desc, in_ptrs, ws_ptr, m: int, K: int):
-        """``enqueue_gather`` on prepared ctypes blocks (bench.py); the shape must be ``mixq_tp_fused_supported``."""
+    def enqueue_gather_raw(self, handle, in_desc, in_ptrs, ws_ptr, m: int, K: int, bias_ptr=None):
+        """``enqueue_gather`` on prepared ctypes blocks (bench.py); the shape must be ``mixq_tp_fused_supported``.
+        ``bias_ptr``: device address of this rank's fp16 [N/tp] bias slice (16-byte aligned), or None."""
         from . import _lib
         assert not self.capturable, "the GEMM-fused transport carries a host-side sequence number"
         par = self._begin(m)
@@ -292,7 +298,11 @@ class PeerGather:
             tp.dst_flags[r] = self._flag_ptr(r, par, self.rank)
         tp.counters = self.small.data_ptr() + 4
         with torch.cuda.device(self.dev):
-            _lib.check(self.lib.mixq_enqueue_tp(handle, in_desc, in_ptrs, ws_ptr, ctypes.byref(tp), st), "mixq_enqueue_tp")
+            if bias_ptr is not None:
+                _lib.check(self.lib.mixq_enqueue_tp_bias(handle, in_desc, in_ptrs, ctypes.c_void_p(bias_ptr), ws_ptr,
+                                                         ctypes.byref(tp), st), "mixq_enqueue_tp_bias")
+            else:
+                _lib.check(self.lib.mixq_enqueue_tp(handle, in_desc, in_ptrs, ws_ptr, ctypes.byref(tp), st), "mixq_enqueue_tp")
             self._wait(par, int(self.lib.mixq_tp_flag_words(m)), st)
         return self._view(par, m)
 

@@ -113,11 +113,13 @@ class MixQPlugin:
         return ws
 
     def enqueue(self, inputs: List[torch.Tensor], output: Optional[torch.Tensor] = None,
-                workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+                workspace: Optional[torch.Tensor] = None, bias: Optional[torch.Tensor] = None) -> torch.Tensor:
         """MixQPlugin::enqueue (TsinghuaMixQPlugin.h:53-54) on the current stream of ``inputs[0].device``.
 
         ``inputs`` are the 7 tensors of plugin.py:141-151, every one declared fp16 exactly as TensorRT sees them
-        (int8 / int32 payloads travel as fp16 views)."""
+        (int8 / int32 payloads travel as fp16 views).  ``bias`` (optional, [N]): cast to fp16 as the reference's
+        ``cast(bias, x.dtype)`` (plugin.py:158-160) and added in the GEMM's epilogue (``mixq_enqueue_bias``): the same
+        bits as ``enqueue(inputs) + bias``, without the second pass over the output."""
         assert len(inputs) == 7, "MixQ takes 7 inputs"
         A = inputs[0]
         if not A.is_cuda:
@@ -140,11 +142,27 @@ class MixQPlugin:
             workspace = self._workspace(A.device, self.workspace_size(max(M, 1), N, K))
         in_ptrs = (ctypes.c_void_p * 7)(*[t.data_ptr() for t in inputs])
         out_ptrs = (ctypes.c_void_p * 1)(output.data_ptr())
+        if bias is not None:
+            bias = fp16_bias(bias, N, A.device)
+            with torch.cuda.device(A.device):
+                rc = self._lib.mixq_enqueue_bias(self._h, in_desc, ctypes.byref(out_desc), in_ptrs, out_ptrs,
+                                                 ctypes.c_void_p(bias.data_ptr()), ctypes.c_void_p(workspace.data_ptr()),
+                                                 _stream_ptr(A.device))
+            _lib.check(rc, "MixQPlugin::enqueue (bias)")
+            return output
         with torch.cuda.device(A.device):  # the library keys its per-device state on the CURRENT device
             rc = self._lib.mixq_enqueue(self._h, in_desc, ctypes.byref(out_desc), in_ptrs, out_ptrs,
                                         ctypes.c_void_p(workspace.data_ptr()), _stream_ptr(A.device))
         _lib.check(rc, "MixQPlugin::enqueue")
         return output
+
+
+def fp16_bias(bias: torch.Tensor, n: int, device) -> torch.Tensor:
+    """The bias operand of the ``*_bias`` entries: fp16 [n] (``cast(bias, x.dtype)``, plugin.py:158-160), contiguous, on
+    ``device``, 16-byte aligned (a misaligned view is copied)."""
+    b = bias.to(device=device, dtype=torch.float16).contiguous().reshape(-1)
+    assert b.numel() == n, f"bias of {b.numel()} elements vs {n} output features"
+    return b if b.data_ptr() % 16 == 0 else b.clone()
 
 
 def mixgemm(m: int, n: int, k: int, inputs: List[torch.Tensor]) -> torch.Tensor:
@@ -177,6 +195,7 @@ class MixQLinear:
         self.peer_gather = None   # optional parallel.PeerGather: one-sided peer writes instead of the RCCL all-gather
         self.peer_gather_alias = False  # True: forward() returns a VIEW of the gather buffer (valid until two more gathers)
         self.weight_image = None  # optional mixlib.WeightImage (prepare_decode_batches): a streaming-friendly copy of `weight`
+        self.fuse_bias = True     # False: the bias is added by a separate torch fp16 add after the operator (same bits; A/B only)
 
     def prepare_decode_batches(self, enable: bool = True):
         """MI355X extension (include/mixq.h ``mixq_weight_image_*``): register a fragment-major copy of ``weight`` so that decode
@@ -217,22 +236,24 @@ class MixQLinear:
     def forward(self, A: torch.Tensor) -> torch.Tensor:
         if self._plugin is None:
             self._plugin = MixQPlugin.create(A.shape[0], self.out_features, self.in_features)
-        if self.tp_size > 1 and self.gather_output and self.peer_gather is not None and self.bias is None:
-            # operator + all-gather in one pass: the GEMM's store path writes this rank's column block into every rank's
-            # buffer (mixq_enqueue_tp); shapes that do not take the 256 x 256 ping-pong kernel fall through to
-            # enqueue + push below
+        fused_bias = self.bias if self.fuse_bias else None
+        if self.tp_size > 1 and self.gather_output and self.peer_gather is not None and (self.bias is None or self.fuse_bias):
+            # operator + all-gather in one pass: the GEMM's store path writes this rank's column block (plus this rank's
+            # bias slice) into every rank's buffer (mixq_enqueue_tp / mixq_enqueue_tp_bias); shapes that do not take the
+            # 256 x 256 ping-pong kernel fall through to enqueue + push below
             g = self.peer_gather.enqueue_gather(self._plugin, [A.contiguous(), self.weight, self.weights_scaling_factor,
                                                                self.fp_weight, self.fp_ind, self.qweight,
-                                                               self.weights_scaling_factor])
+                                                               self.weights_scaling_factor], bias=fused_bias)
             if g is not None:
                 g = g.reshape(*A.shape[:-1], self.out_features * self.tp_size)
                 return g if self.peer_gather_alias else g.clone()
+        # plugin.py:158-160 adds the bias after its collective; the bias of a row-sharded layer is this rank's [N/tp] slice
+        # (parallel.shard_packed), so it is added to the shard BEFORE the gather -- the same fp16 additions, element for
+        # element, as adding the full bias to the gathered output.  By default in the GEMM's epilogue (mixq_enqueue_bias,
+        # bit-identical to the separate add below, which fuse_bias = False keeps for A/B measurements)
         x = self._plugin.enqueue([A, self.weight, self.weights_scaling_factor, self.fp_weight, self.fp_ind,
-                                  self.qweight, self.weights_scaling_factor])   # plugin.py:141-151
-        if self.bias is not None:
-            # plugin.py:158-160 adds the bias after its collective; the bias of a row-sharded layer is this rank's
-            # [N/tp] slice (parallel.shard_packed), so it is added to the shard BEFORE the gather -- the same fp16
-            # additions, element for element, as adding the full bias to the gathered output
+                                  self.qweight, self.weights_scaling_factor], bias=fused_bias)   # plugin.py:141-151
+        if self.bias is not None and fused_bias is None:
             x = x + self.bias.to(x.dtype)
         if self.tp_size > 1 and self.gather_output:
             # The reference calls allreduce here (plugin.py:155-156), which is shape-wrong for an N-split and is
