@@ -251,7 +251,9 @@ MIXQ_API int mixq_weight_image_stale_count(void);
  * at lane * 16, the 16 bytes (row t * 16 + lane % 16, k = s * 64 + (lane / 16) * 16 ...) -- each qA load of that kernel becomes one
  * contiguous 1-KiB read instead of 16 rows x 64 bytes 4 KiB apart: 32 x 4096 x 4096 GEMM 7.9 -> 5.4 us (BASELINE configs[0]
  * 11.8 -> 9.2 us through mixq_enqueue, which uses it internally).  The image is opaque (mixq_qa_bytes bytes, 16-byte aligned)
- * and has ONE reader: passing it for a shape the skinny kernel does not serve returns MIXQ_E_SHAPE.  Same bits as row-major. */
+ * and has ONE reader: passing it for a shape the skinny kernel does not serve returns MIXQ_E_SHAPE.  Same bits as row-major.
+ * The producers write the bytes of the M x K elements only: the padding of a partial last 16-row tile (rows M..) and of a partial
+ * last k-step (k = K..) keeps whatever the buffer held, and the reader never lets it reach its output. */
 #define MIXQ_QA_ROW_MAJOR 0
 #define MIXQ_QA_FRAGMENT_MAJOR 1
 MIXQ_API int mixq_qa_layout(int M, int N, int K);               /* the layout to produce for a [M,K] x [N,K]^T consumer without scratch */
@@ -517,6 +519,11 @@ MIXQ_API void mixq_debug_set_stamp_buffer(void* device_u64_8_per_block);
 MIXQ_API void mixq_debug_set_quant_stamp_buffer(void* device_u64_8_per_block);
 /* Reporting only: name of the kernel family the fused GEMM selected on its most recent launch in this process. */
 MIXQ_API const char* mixq_debug_last_gemm_kernel(void);
+/* Reporting only: the form the most recent activation-producer launch of this process took -- kernel, threads per row (TPR),
+ * 16-byte vectors per lane (MAXV), outlier zeroing (ZERO) or quantisation (QUANT), fragment-major qA (FRAG), " nt" when the qA
+ * stores are non-temporal -- e.g. "quant_extract_kernel<TPR=64,MAXV=8,ZERO=1,FRAG=0>", "quant_extract_long_kernel<ZERO=0>",
+ * "rmsnorm_quant_kernel<TPR=256,MAXV=2,QUANT=4,FRAG=0>", "quant4_rows_kernel". */
+MIXQ_API const char* mixq_debug_last_producer_kernel(void);
 MIXQ_API const char* mixq_version(void);
 /* ABI revision of THIS header.  It is bumped whenever an exported entry changes its argument list in place (revision 3: the
  * mixq_tp_buffer_alloc / mixq_tp_push_columns / mixq_tp_wait signatures of round 3), so that a host built against an older

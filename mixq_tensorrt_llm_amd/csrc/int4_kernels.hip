@@ -107,6 +107,7 @@ __global__ __launch_bounds__(I4BLOCK) void unpack_s4_columns_kernel(const uint8_
 hipError_t launch_quant4_rows(const void* A, uint8_t* q, void* sA, int M, int K, hipStream_t st)
 {
     if (M <= 0) return hipSuccess;
+    note_producer_kernel("quant4_rows_kernel");
     hipLaunchKernelGGL(quant4_rows_kernel, dim3((unsigned)M), dim3(I4BLOCK), 0, st, static_cast<const uint16_t*>(A), q,
                        static_cast<uint16_t*>(sA), M, K);
     return hipGetLastError();

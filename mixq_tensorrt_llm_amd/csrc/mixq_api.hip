@@ -166,6 +166,7 @@ void mixq_debug_reset(void)
 }
 
 const char* mixq_debug_last_gemm_kernel(void) { return mixq::last_gemm_kernel(); }
+const char* mixq_debug_last_producer_kernel(void) { return mixq::last_producer_kernel(); }
 
 const char* mixq_version(void) { return "mixq-mi355x 0.3 (gfx950)"; }
 int mixq_abi_version(void) { return MIXQ_ABI_VERSION; }

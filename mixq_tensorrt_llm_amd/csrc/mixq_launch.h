@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include <atomic>
+#include <string>
 
 namespace mixq {
 
@@ -179,6 +180,11 @@ bool gemm_takes_skinny(const GemmParams& p, int epi);
 bool qa_frag_enabled(); // test knob 890 / 891 (default on)
 bool probe_a2();        // timing probe 898 / 899 // launch_gemm would run gemm_skinny_kernel on this problem
 void set_quant_stamp_buffer(void* device_u64_8_per_block); // measurement only (NULL in production)
+// Activation producers (quantisers, outlier gathers, the fused RMSNorm producer): name of the form the most recent launch took,
+// e.g. "quant_extract_kernel<TPR=64,MAXV=8,ZERO=1,FRAG=0> nt" (" nt": non-temporal qA stores).  Reporting only.
+const char* last_producer_kernel();
+void note_producer_kernel(const char* name); // (name: a string that lives as long as the process)
+std::string producer_form_name(const char* kernel, int tpr, int maxv, const char* flag, int flag_value, int frag, bool nt);
 hipError_t launch_quant_with_scale(const void* src, const void* scale, int8_t* dst, int M, int K, hipStream_t st);
 hipError_t launch_extract(void* A, void* fpA, const int32_t* ind, int M, int K, int O, bool zero, hipStream_t st);
 hipError_t launch_rmsnorm_quant(const void* X, const void* gamma, void* out, void* outl, const int32_t* ind, int8_t* q,

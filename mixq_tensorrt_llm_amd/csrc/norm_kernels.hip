@@ -229,6 +229,15 @@ __global__ __launch_bounds__(NBLOCK) void rmsnorm_quant_kernel(const uint16_t* _
     }
 }
 
+// one name per instantiation and store form, built on its first launch (reporting only: mixq_debug_last_producer_kernel)
+template <int TPR, int MAXV, int QUANT, bool FRAG>
+static void note_norm(bool nt)
+{
+    static const std::string n[2] = {producer_form_name("rmsnorm_quant_kernel", TPR, MAXV, "QUANT", QUANT, FRAG, false),
+                                     producer_form_name("rmsnorm_quant_kernel", TPR, MAXV, "QUANT", QUANT, FRAG, true)};
+    note_producer_kernel(n[nt ? 1 : 0].c_str());
+}
+
 template <int TPR, int MAXV>
 static hipError_t launch_norm(const uint16_t* X, const uint16_t* gamma, uint16_t* out, uint16_t* outl,
                               const int32_t* ind, int8_t* q, uint16_t* scale, float eps, int M, int K, int O,
@@ -240,6 +249,7 @@ static hipError_t launch_norm(const uint16_t* X, const uint16_t* gamma, uint16_t
             static DeviceOnce oncef;
             if (hipError_t e = ensure_dynamic_lds(rmsnorm_quant_kernel<TPR, MAXV, 8, true>, 160 * 1024 - 64, oncef); e != hipSuccess)
                 return e;
+            note_norm<TPR, MAXV, 8, true>(false);
             hipLaunchKernelGGL((rmsnorm_quant_kernel<TPR, MAXV, 8, true>), dim3((unsigned)M), dim3(NBLOCK), lds, st, X, gamma, out,
                                outl, ind, q, scale, eps, M, K, O);
             return hipGetLastError();
@@ -256,6 +266,8 @@ static hipError_t launch_norm(const uint16_t* X, const uint16_t* gamma, uint16_t
             return e;
         if (hipError_t e = ensure_dynamic_lds(rmsnorm_quant_kernel<TPR, MAXV, 4>, 160 * 1024 - 64, once4); e != hipSuccess)
             return e;
+        if (quant == 4) note_norm<TPR, MAXV, 4, false>(false);
+        else note_norm<TPR, MAXV, 8, false>((int64_t)M * K >= ((int64_t)8 << 20)); // (the kernel's stream_out)
         if (quant == 4)
             hipLaunchKernelGGL((rmsnorm_quant_kernel<TPR, MAXV, 4>), grid, block, lds, st, X, gamma, out, outl, ind, q,
                                scale, eps, M, K, O);
@@ -263,6 +275,7 @@ static hipError_t launch_norm(const uint16_t* X, const uint16_t* gamma, uint16_t
             hipLaunchKernelGGL((rmsnorm_quant_kernel<TPR, MAXV, 8>), grid, block, lds, st, X, gamma, out, outl, ind, q,
                                scale, eps, M, K, O);
     } else {
+        note_norm<TPR, MAXV, 0, false>(false);
         hipLaunchKernelGGL((rmsnorm_quant_kernel<TPR, MAXV, 0>), grid, block, 0, st, X, gamma, out, outl, ind, q,
                            scale, eps, M, K, O);
     }

@@ -115,6 +115,7 @@ __global__ __launch_bounds__(QBLOCK) void quant_extract_kernel(uint16_t* __restr
         amax = -1;           // (-1 = every element is NaN)
 #pragma unroll
         for (int v = 0; v < MAXV; ++v) {
+            if (v * TPR + t >= nvec) continue; // (the zero vectors past the row's end are not elements: an all-NaN row keeps -1)
             const unsigned w[4] = {x[v].x, x[v].y, x[v].z, x[v].w};
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
@@ -293,6 +294,7 @@ hipError_t launch_quant_with_scale(const void* src, const void* scale, int8_t* d
     const int64_t total = (int64_t)M * (K / 8);
     const int64_t want = (total + QBLOCK - 1) / QBLOCK;
     const unsigned grid = (unsigned)(want < 4096 ? want : 4096);
+    note_producer_kernel("quant_with_scale_kernel");
     hipLaunchKernelGGL(quant_with_scale_kernel, dim3(grid), dim3(QBLOCK), 0, st, static_cast<const uint16_t*>(src),
                        static_cast<const uint16_t*>(scale), dst, M, K);
     return hipGetLastError();
@@ -300,6 +302,23 @@ hipError_t launch_quant_with_scale(const void* src, const void* scale, int8_t* d
 
 static std::atomic<void*> g_quant_stamps{nullptr}; // measurement only (tools/small_m_timeline.py)
 void set_quant_stamp_buffer(void* p) { g_quant_stamps.store(p); }
+
+static std::atomic<const char*> g_last_producer{"none"}; // reporting only (mixq_debug_last_producer_kernel)
+const char* last_producer_kernel() { return g_last_producer.load(std::memory_order_relaxed); }
+void note_producer_kernel(const char* name) { g_last_producer.store(name, std::memory_order_relaxed); }
+std::string producer_form_name(const char* kernel, int tpr, int maxv, const char* flag, int flag_value, int frag, bool nt)
+{
+    return std::string(kernel) + "<TPR=" + std::to_string(tpr) + ",MAXV=" + std::to_string(maxv) + "," + flag + "=" +
+           std::to_string(flag_value) + ",FRAG=" + std::to_string(frag) + ">" + (nt ? " nt" : "");
+}
+// one name per instantiation and store form, built on its first launch
+template <int TPR, int MAXV, bool ZERO, int FRAG>
+static void note_qe(bool nt)
+{
+    static const std::string n[2] = {producer_form_name("quant_extract_kernel", TPR, MAXV, "ZERO", ZERO, FRAG, false),
+                                     producer_form_name("quant_extract_kernel", TPR, MAXV, "ZERO", ZERO, FRAG, true)};
+    note_producer_kernel(n[nt ? 1 : 0].c_str());
+}
 
 template <int TPR, int MAXV>
 static hipError_t launch_qe(uint16_t* A, int8_t* qA, uint16_t* sA, uint16_t* fpA, const int32_t* ind, int M, int K,
@@ -309,6 +328,8 @@ static hipError_t launch_qe(uint16_t* A, int8_t* qA, uint16_t* sA, uint16_t* fpA
     if constexpr (TPR == 256 && MAXV <= 8) {
         if (frag == 1) { // decode batches: qA in the skinny GEMM's fragment order (both flavours)
             dim3 grid((unsigned)M), block(QBLOCK);
+            if (zero) note_qe<TPR, MAXV, true, 1>(false);
+            else note_qe<TPR, MAXV, false, 1>(false);
             if (zero)
                 hipLaunchKernelGGL((quant_extract_kernel<TPR, MAXV, true, 1>), grid, block, (size_t)((K + 31) / 32) * 4, st, A, qA, sA,
                                    fpA, ind, M, K, O, zw, dbg);
@@ -320,10 +341,13 @@ static hipError_t launch_qe(uint16_t* A, int8_t* qA, uint16_t* sA, uint16_t* fpA
     if (frag != 0) return hipErrorInvalidValue;
     constexpr int RPB = QBLOCK / TPR;
     dim3 grid((unsigned)((M + RPB - 1) / RPB)), block(QBLOCK);
+    const bool nt = (int64_t)M * K >= ((int64_t)8 << 20); // (the kernel's stream_out)
     if (zero) {
+        note_qe<TPR, MAXV, true, 0>(nt);
         size_t sm = (size_t)((K + 31) / 32) * 4;
         hipLaunchKernelGGL((quant_extract_kernel<TPR, MAXV, true>), grid, block, sm, st, A, qA, sA, fpA, ind, M, K, O, zw, dbg);
     } else {
+        note_qe<TPR, MAXV, false, 0>(nt);
         hipLaunchKernelGGL((quant_extract_kernel<TPR, MAXV, false>), grid, block, 0, st, A, qA, sA, fpA, ind, M, K, O, zw, dbg);
     }
     return hipGetLastError();
@@ -372,9 +396,11 @@ hipError_t launch_quant_extract(void* A, int8_t* qA, void* sA, void* fpA, const 
     if (nvec <= 256 * 16) return launch_qe<256, 16>(a, qA, s, f, ind, M, K, O, zero, st, zw, frag);
     dim3 grid((unsigned)M), block(QBLOCK);
     if (zero) {
+        note_producer_kernel("quant_extract_long_kernel<ZERO=1>");
         size_t sm = (size_t)((K + 31) / 32) * 4;
         hipLaunchKernelGGL((quant_extract_long_kernel<true>), grid, block, sm, st, a, qA, s, f, ind, M, K, O, zw);
     } else {
+        note_producer_kernel("quant_extract_long_kernel<ZERO=0>");
         hipLaunchKernelGGL((quant_extract_long_kernel<false>), grid, block, 0, st, a, qA, s, f, ind, M, K, O, zw);
     }
     return hipGetLastError();
@@ -384,6 +410,7 @@ hipError_t launch_extract(void* A, void* fpA, const int32_t* ind, int M, int K, 
 {
     if (M <= 0 || O <= 0) return hipSuccess;
     dim3 grid((unsigned)((M + 3) / 4)), block(QBLOCK);
+    note_producer_kernel(zero ? "extract_kernel<ZERO=1>" : "extract_kernel<ZERO=0>");
     if (zero)
         hipLaunchKernelGGL((extract_kernel<true>), grid, block, 0, st, static_cast<uint16_t*>(A),
                            static_cast<uint16_t*>(fpA), ind, M, K, O);

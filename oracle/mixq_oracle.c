@@ -163,6 +163,18 @@ ORACLE_API void mixq_oracle_quant_rows(int64_t M, int64_t K, const uint16_t* A, 
     }
 }
 
+/*
+ * quantkernel/mix_cuda/cult.cu:1732-1771 Int8quantize: the same per-element step as quant_rows with a caller-supplied
+ * per-row scale -- no amax, no clamp, no zero guard:
+ *   qA[m,k] = (int8) __half2int_rn(__hdiv(A[m,k], scale[m]))
+ */
+ORACLE_API void mixq_oracle_quant_with_scale(int64_t M, int64_t K, const uint16_t* A, const uint16_t* scale, int8_t* qA)
+{
+#pragma omp parallel for schedule(static)
+    for (int64_t m = 0; m < M; ++m)
+        for (int64_t k = 0; k < K; ++k) qA[m * K + k] = (int8_t)h2int_rn(h_div(A[m * K + k], scale[m]));
+}
+
 /* ---------------------------------------------- a2: outlier extraction -- */
 /*
  * kernel/i8gemm.cu:198-244: fp_A[m, j] = A[m, ind[j]], A left untouched (line 218 commented out).

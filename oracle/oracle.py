@@ -18,7 +18,7 @@ __all__ = [
     "select_outliers", "pack_linear_weights", "eetq_symmetric_quantize", "eetq_preprocess", "w8a16_gemv",
     "int_to_half", "int8_matrix_to_half", "rmsnorm_extract_quant", "find_outliers", "dequant_weight_columns",
     "MixLinearState", "mixlinear_forward", "quant4_rows", "unpack_i4", "pack_i4", "mixlinear4_from_linear",
-    "mixlinear4_forward", "hdiv_cuda", "quant_rows_cuda_hdiv",
+    "mixlinear4_forward", "hdiv_cuda", "quant_rows_cuda_hdiv", "quant_with_scale",
 ]
 
 
@@ -104,6 +104,17 @@ def quant_rows(A, zero_cols=None):
     lib().mixq_oracle_quant_rows(_i64(M), _i64(K), _p(A), _p(qA), _p(sA), _p(zc),
                                  ctypes.c_int(0 if zc is None else zc.size))
     return qA, sA
+
+
+def quant_with_scale(A, scale):
+    """cult.cu:1732-1771 Int8quantize: (int8) half2int_rn(hdiv(A, scale[row])) with a given fp16 scale per row -> qA int8 [M,K]."""
+    A = _h(A)
+    M, K = A.shape
+    scale = np.ascontiguousarray(np.asarray(scale, np.float16).reshape(-1))
+    assert scale.size == M, (scale.size, M)
+    qA = np.empty((M, K), np.int8)
+    lib().mixq_oracle_quant_with_scale(_i64(M), _i64(K), _p(A), _p(scale), _p(qA))
+    return qA
 
 
 def hdiv_cuda(a, b, rcp_ulps=0):
@@ -429,6 +440,7 @@ def quant4_rows(A):
         amax = np.where(np.isnan(absA).all(axis=1), np.float16(np.nan),
                         np.nanmax(np.where(np.isnan(absA), np.float16(-1), absA), axis=1)).astype(np.float16)
         s = (amax / np.float16(7)).astype(np.float16)
+        s = np.where(np.isnan(s), np.uint16(0x7fff).view(np.float16), s)   # __hmax of two NaNs and __hdiv of a NaN: canonical 0x7fff
         qh = (A / s[:, None]).astype(np.float16)                    # __hdiv: correctly rounded fp16 quotient
         r = np.rint(qh.astype(np.float64))                           # __half2int_rn: RNE
         r = np.where(np.isnan(r), 0, np.clip(r, -2147483648, 2147483647))   # NaN -> 0, +-inf saturate

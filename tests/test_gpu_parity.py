@@ -98,7 +98,8 @@ def test_quant_every_fp16_value_against_many_scales(oracle):
     assert np.array_equal(bits(s.cpu().numpy()), bits(so))
     bad = np.argwhere(q != qo)
     assert bad.size == 0, f"{len(bad)} mismatches, first {bad[:3].tolist()}"
-    # the wave-per-row kernels (K <= 8192) use the same shortcut: random rows with many scales
+    # random rows with many scales at 512 x 4096: under the default rule (block-per-row up to 2048 rows at this K) that is the 256 x 2
+    # block-per-row form; the wavefront-per-row forms run in tests/test_gpu_producers.py
     B = (rng.standard_normal((512, 4096)) * np.exp(rng.uniform(-6, 6, (512, 1)))).astype(np.float16)
     xb = to_dev(B)
     sb = torch.empty(512, dtype=torch.float16, device=dev())

@@ -88,6 +88,42 @@ def test_quant_rows_against_numpy_float16(oracle):
     assert np.abs(qA[[0, 1, 3, 6, 7, 8]].astype(np.int32)).max() == 127
 
 
+def test_quant_with_scale_against_numpy_float16(oracle):
+    """Int8quantize's oracle: (int8) half2int_rn(hdiv(x, scale[row])), the element step of quant_rows with the scale given --
+    numpy's correctly rounded float16 division, including the scales a caller may pass that quant_rows never derives."""
+    rng = np.random.default_rng(11)
+    A = (rng.standard_normal((8, 264)) * 40).astype(np.float16)
+    A[:, 0] = 0
+    A[:, 1] = np.float16(65504)
+    A[:, 2] = -np.inf
+    A[:, 3] = np.nan
+    A[:, 4] = np.float16(6e-8)
+    s = np.float16([0.1, 0.0, -0.0, 6e-8, np.inf, np.nan, 1e-3, 517.0])
+    q = oracle.quant_with_scale(A, s)
+    with np.errstate(all="ignore"):
+        h = (A / s[:, None]).astype(np.float16).astype(np.float32)
+        want = np.where(np.isnan(h), 0, np.where(np.isinf(h), np.where(h > 0, 2**31 - 1, -2**31), np.rint(h)))
+        want = (want.astype(np.int64) & 0xff).astype(np.uint8).view(np.int8)
+    assert np.array_equal(q, want)
+    assert q[1, 1] == -1 and q[1, 0] == 0 and q[1, 2] == 0      # x / 0: +inf -> INT_MAX -> -1; 0 / 0 = NaN -> 0; -inf -> INT_MIN -> 0
+    assert np.all(q[5] == 0) and np.all(q[:, 3] == 0)          # NaN quotients -> 0
+    # with the scales quant_rows derives, the rows quant_rows writes
+    qo, so = oracle.quant_rows(A)
+    assert np.array_equal(oracle.quant_with_scale(A, so), qo)
+
+
+def test_all_nan_row_scale_is_the_canonical_nan(oracle):
+    """__hmax of two NaNs returns the canonical NaN 0x7fff and __hdiv passes it on: an all-NaN row's scale has those bits in the
+    8-bit and the 4-bit quantiser alike (its elements quantise to 0)."""
+    A = np.full((2, 24), np.nan, np.float16)
+    A[1, :12] = np.float16(1.5)
+    q8, s8 = oracle.quant_rows(A)
+    q4, s4 = oracle.quant4_rows(A)
+    assert s8.view(np.uint16)[0] == 0x7fff and s4.view(np.uint16)[0] == 0x7fff
+    assert np.all(q8[0] == 0) and np.all(q4[0] == 0)
+    assert not np.isnan(s8[1]) and not np.isnan(s4[1])
+
+
 def test_linear_prefill_against_float64(oracle):
     from conftest import make_layer
     A, W, act = make_layer(37, 256, 512, seed=5)
