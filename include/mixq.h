@@ -33,6 +33,7 @@ enum {
     MIXQ_E_HIP = 4,       /* a HIP launch failed; hipGetLastError() has the detail */
     MIXQ_E_WORKSPACE = 5, /* workspace pointer is null where one is needed */
     MIXQ_E_STALE = 6,     /* mixq_weight_image_verify: the bytes behind a registered weight pointer are not the registered weight's */
+    MIXQ_E_TYPE = 7,      /* descriptor types are not a supported combination (a bf16 call with a non-bf16 fp_weight / output, bf16 on TP) */
 };
 
 /* ---- tensor descriptor ------------------------------------------------------------------------ */
@@ -47,7 +48,8 @@ typedef struct mixq_tensor_desc {
     int32_t format; /* MIXQ_FORMAT_LINEAR */
     float scale;
 } mixq_tensor_desc;
-enum { MIXQ_TYPE_FLOAT = 0, MIXQ_TYPE_HALF = 1, MIXQ_TYPE_INT8 = 2, MIXQ_TYPE_INT32 = 3 }; /* nvinfer1::DataType values */
+enum { MIXQ_TYPE_FLOAT = 0, MIXQ_TYPE_HALF = 1, MIXQ_TYPE_INT8 = 2, MIXQ_TYPE_INT32 = 3,
+       MIXQ_TYPE_BF16 = 7 }; /* nvinfer1::DataType values (7 = kBF16) */
 enum { MIXQ_FORMAT_LINEAR = 0 };
 
 /* nvinfer1::PluginField mirror for the creator path (TsinghuaMixQPlugin.cpp:895-933 reads "m","n","k" INT32). */
@@ -95,10 +97,15 @@ MIXQ_API int mixq_get_nb_outputs(const mixq_handle* h); /* 1, .cpp:785-788 */
 /* getOutputDimensions (.cpp:244-261): out = in0.dims with last dim replaced by in1.d[0]. */
 MIXQ_API int mixq_get_output_dimensions(const mixq_handle* h, int outputIndex, const mixq_tensor_desc* inputs,
                                         int nbInputs, mixq_tensor_desc* out);
-/* supportsFormatCombination (.cpp:263-320): pos 0..7 must be HALF + LINEAR. 1 = supported. */
+/* supportsFormatCombination (.cpp:263-320): pos 0..7 must be HALF + LINEAR. 1 = supported.
+ * MI355X extension (bf16 calls): pos 0 (A) may be BF16 as well; pos 3 (fp_weight) and pos 7 (the output) must then have the type of
+ * inOut[0]; every other position stays HALF. */
 MIXQ_API int mixq_supports_format_combination(const mixq_handle* h, int pos, const mixq_tensor_desc* inOut,
                                               int nbInputs, int nbOutputs);
 MIXQ_API int mixq_get_output_data_type(const mixq_handle* h, int index); /* MIXQ_TYPE_HALF, .cpp:768-773 */
+/* getOutputDataType(index, inputTypes, nbInputs) with TensorRT's full signature: MIXQ_TYPE_BF16 when inputTypes[0] is BF16, else
+ * MIXQ_TYPE_HALF (also for a null inputTypes or nbInputs < 1). */
+MIXQ_API int mixq_get_output_data_type_for(const mixq_handle* h, int index, const int32_t* inputTypes, int nbInputs);
 
 /* ---- workspace -------------------------------------------------------------------------------- */
 /* configurePlugin + getWorkspaceSize (.cpp:325-378).  Bytes this implementation needs for M <= maxM:
@@ -121,6 +128,11 @@ MIXQ_API size_t mixq_reference_workspace_size(int64_t maxM, int64_t N, int64_t K
  * Asynchronous on `stream`. */
 MIXQ_API int mixq_enqueue(const mixq_handle* h, const mixq_tensor_desc* inputDesc, const mixq_tensor_desc* outputDesc,
                           const void* const* inputs, void* const* outputs, void* workspace, void* stream);
+/* bf16 calls (MI355X extension): inputDesc[0].type == MIXQ_TYPE_BF16 makes inputs[0] (A), inputs[3] (fp_weight), outputs[0] and the
+ * bias of mixq_enqueue_bias bf16; inputs 1, 2, 4, 5, 6 are unchanged (weights_scaling_factor and scaling_factors stay fp16).  Same
+ * kernels, tile widths, split factors and workspace as the fp16 call of that shape; DESIGN.md §1 (bf16 calls) defines the result.
+ * inputDesc[3].type != BF16, or a non-null outputDesc whose type is not BF16: MIXQ_E_TYPE before anything is launched.  Any other
+ * inputDesc[0].type is the fp16 call, bit for bit.  (mixq_enqueue_tp / _tp_bias refuse BF16 with MIXQ_E_TYPE.) */
 
 /* Same work, same launches; additionally records two caller-owned hipEvent_t (may be NULL) on `stream` immediately
  * before and after the fused-GEMM launch of the prefill path, so a harness can time the dominant kernel inside its

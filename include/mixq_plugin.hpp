@@ -80,10 +80,10 @@ public:
     {
         return mixq_enqueue_bias(h_, inputDesc, outputDesc, inputs, outputs, bias_f16, workspace, stream);
     }
-    /* IPluginV2Ext */
-    int getOutputDataType(int index, const int* /*inputTypes*/, int /*nbInputs*/) const noexcept /* .cpp:768-773 */
+    /* IPluginV2Ext: HALF (.cpp:768-773), or BF16 when input 0 is BF16 (mixq_get_output_data_type_for: bf16 calls) */
+    int getOutputDataType(int index, const int* inputTypes, int nbInputs) const noexcept
     {
-        return mixq_get_output_data_type(h_, index);
+        return mixq_get_output_data_type_for(h_, index, reinterpret_cast<const int32_t*>(inputTypes), nbInputs);
     }
     /* IPluginV2 */
     const char* getPluginType() const noexcept { return mixq_plugin_type(); }            /* "MixQ" */

@@ -11,11 +11,13 @@ LIB_PATH = os.path.join(_HERE, "libmixq_mi355x.so")
 
 MIXQ_MAX_DIMS = 8
 MIXQ_TYPE_HALF = 1
+MIXQ_TYPE_BF16 = 7   # nvinfer1::DataType::kBF16: A, fp_weight, the output and the bias of a bf16 call
+MIXQ_E_TYPE = 7      # descriptor types are not a supported combination
 MIXQ_FORMAT_LINEAR = 0
 MIXQ_FIELD_INT32 = 3
 
 ERRORS = {0: "ok", 1: "bad argument", 2: "unsupported shape", 3: "pointer not 16-byte aligned", 4: "HIP error",
-          5: "workspace missing"}
+          5: "workspace missing", 7: "descriptor types are not a supported combination"}
 
 
 class MixQLibraryError(RuntimeError):
@@ -35,6 +37,8 @@ class TensorDesc(ctypes.Structure):
 
     @classmethod
     def make(cls, shape, dtype=MIXQ_TYPE_HALF):
+        """`dtype`: the descriptor's nvinfer1::DataType value (MIXQ_TYPE_HALF, or MIXQ_TYPE_BF16 on A / fp_weight / the output of a
+        bf16 call)."""
         t = cls()
         t.nbDims = len(shape)
         for i, s in enumerate(shape):
@@ -80,6 +84,7 @@ SIGNATURES = {
     "mixq_get_output_dimensions": (_i, [_vp, _i, ctypes.POINTER(TensorDesc), _i, ctypes.POINTER(TensorDesc)]),
     "mixq_supports_format_combination": (_i, [_vp, _i, ctypes.POINTER(TensorDesc), _i, _i]),
     "mixq_get_output_data_type": (_i, [_vp, _i]),
+    "mixq_get_output_data_type_for": (_i, [_vp, _i, ctypes.POINTER(ctypes.c_int32), _i]),
     "mixq_workspace_size": (_sz, [_vp, _i64, _i64, _i64]),
     "mixq_reference_workspace_size": (_sz, [_i64, _i64, _i64]),
     "mixq_enqueue_scratch_size": (_sz, [_i64, _i64, _i64]),

@@ -41,16 +41,28 @@ def to_carriers(packed: Dict[str, np.ndarray]) -> Dict[str, torch.Tensor]:
     def view16(a, shape):
         return torch.from_numpy(np.ascontiguousarray(a)).view(torch.float16).reshape(shape).clone()
 
+    def fp_or_bf16(a, shape):  # uint16 arrays are bf16 bit patterns (pack_linear_weights(fp_dtype=torch.bfloat16)): stored as bf16
+        if a.dtype == np.uint16:
+            return torch.from_numpy(np.ascontiguousarray(a).view(np.int16)).view(torch.bfloat16).reshape(shape).clone()
+        return view16(a.astype(np.float16), shape)
+
     out = {
         "weight": view16(packed["weight"].astype(np.int8), (N, K // 2)),
         "weights_scaling_factor": view16(packed["weights_scaling_factor"].astype(np.float16), (N,)),
-        "fp_weight": view16(packed["fp_weight"].astype(np.float16), (N, packed["fp_weight"].shape[1])),
+        "fp_weight": fp_or_bf16(packed["fp_weight"], (N, packed["fp_weight"].shape[1])),
         "fp_ind": view16(packed["fp_ind"].astype(np.int32), (2 * packed["fp_ind"].size,)),
         "qweight": view16(packed["qweight"].astype(np.uint8), (K, N // 2)),
     }
     if packed.get("bias") is not None:
-        out["bias"] = torch.from_numpy(np.ascontiguousarray(packed["bias"]))
+        b = np.ascontiguousarray(packed["bias"])
+        out["bias"] = fp_or_bf16(b, b.shape) if b.dtype == np.uint16 else torch.from_numpy(b)
     return out
+
+
+def _np_bits(t: torch.Tensor) -> np.ndarray:
+    """A tensor as numpy: bf16 as its uint16 bit patterns (numpy has no bf16), anything else as is."""
+    t = t.contiguous()
+    return t.view(torch.int16).numpy().view(np.uint16) if t.dtype == torch.bfloat16 else t.numpy()
 
 
 def from_carriers(t: Dict[str, torch.Tensor]) -> Dict[str, np.ndarray]:
@@ -60,12 +72,12 @@ def from_carriers(t: Dict[str, torch.Tensor]) -> Dict[str, np.ndarray]:
     out = {
         "weight": t["weight"].contiguous().view(torch.int8).reshape(N, K).numpy(),
         "weights_scaling_factor": t["weights_scaling_factor"].contiguous().numpy(),
-        "fp_weight": t["fp_weight"].contiguous().numpy(),
+        "fp_weight": _np_bits(t["fp_weight"]),
         "fp_ind": t["fp_ind"].contiguous().view(torch.int32).numpy(),
         "qweight": t["qweight"].contiguous().view(torch.uint8).reshape(K, N).numpy(),
     }
     if "bias" in t:
-        out["bias"] = t["bias"].numpy()
+        out["bias"] = _np_bits(t["bias"])
     return out
 
 

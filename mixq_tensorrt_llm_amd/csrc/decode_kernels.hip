@@ -189,6 +189,155 @@ static hipError_t launch_w8a16_rows(const void* A, const uint8_t* Wq, const void
     return hipSuccess;
 }
 
+// ---- bf16 calls: Out[m,n] = bf16(scale[n] * sum_k fp32(A[m,k]) (q[k,n] - 128)) ------------------------------------------
+// Same layout walk, grid and reduction as w8a16_gemv_kernel.  The weight element q - 128 (|q - 128| <= 128) is exact in bf16, so
+// a pair of them goes into v_dot2_f32_bf16 with the pair of bf16 activations (exact products, fp32 sums), and the fp16 column
+// scale multiplies the fp32 sum once -- nothing is rounded below fp32 before the single bf16 rounding of the result.
+template <int MB, int WPP, int PPW, bool BIAS>
+__global__ __launch_bounds__(256) void w8a16_gemv_bf16_kernel(const uint16_t* __restrict__ A, const uint8_t* __restrict__ Wq,
+                                                               const uint16_t* __restrict__ scale, uint16_t* __restrict__ Out, int N,
+                                                               int K, const uint16_t* __restrict__ bias)
+{
+    constexpr int GPB = 4 / WPP;
+    __shared__ float red[4][PPW][MB][2];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int pair0 = (blockIdx.x * GPB + wave / WPP) * PPW;
+    const int part = wave % WPP;
+    const int col = (lane >> 2) & 1;
+    const int npairs = N / 2;
+    const uint8_t* wrow[PPW];
+#pragma unroll
+    for (int q = 0; q < PPW; ++q) wrow[q] = Wq + (int64_t)min(pair0 + q, npairs - 1) * 2 * K; // (clamped pairs are never stored)
+    float acc[PPW][MB];
+#pragma unroll
+    for (int q = 0; q < PPW; ++q)
+#pragma unroll
+        for (int m = 0; m < MB; ++m) acc[q][m] = 0.f;
+    const int nsteps = (2 * K) >> 10;
+    auto step = [&](int byte0) __attribute__((always_inline)) {
+        uint4 wv[PPW];
+#pragma unroll
+        for (int q = 0; q < PPW; ++q) wv[q] = *reinterpret_cast<const uint4*>(wrow[q] + byte0);
+        const int kbase = (byte0 >> 7) * 64 + (byte0 & 63);
+        unsigned aw[MB][8];
+#pragma unroll
+        for (int m = 0; m < MB; ++m) {
+            const uint4 a0 = *reinterpret_cast<const uint4*>(A + (int64_t)m * K + kbase);
+            const uint4 a1 = *reinterpret_cast<const uint4*>(A + (int64_t)m * K + kbase + 8);
+            aw[m][0] = a0.x, aw[m][1] = a0.y, aw[m][2] = a0.z, aw[m][3] = a0.w;
+            aw[m][4] = a1.x, aw[m][5] = a1.y, aw[m][6] = a1.z, aw[m][7] = a1.w;
+        }
+#pragma unroll
+        for (int q = 0; q < PPW; ++q) {
+            const unsigned w[4] = {wv[q].x, wv[q].y, wv[q].z, wv[q].w};
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const v2bf wl = __builtin_bit_cast(v2bf, wpair_bf16(w[j], 0, 2)); // k = 2j, 2j+1
+                const v2bf wh = __builtin_bit_cast(v2bf, wpair_bf16(w[j], 1, 3)); // k = 8+2j, 9+2j
+#pragma unroll
+                for (int m = 0; m < MB; ++m) {
+                    acc[q][m] = __builtin_amdgcn_fdot2_f32_bf16(wl, __builtin_bit_cast(v2bf, aw[m][j]), acc[q][m], false);
+                    acc[q][m] = __builtin_amdgcn_fdot2_f32_bf16(wh, __builtin_bit_cast(v2bf, aw[m][4 + j]), acc[q][m], false);
+                }
+            }
+        }
+    };
+    {
+        int st = part;
+        for (; st < nsteps; st += WPP) step((st << 10) + lane * 16);
+        const int tail0 = nsteps << 10;
+        if (part == 0 && tail0 + lane * 16 < 2 * K) step(tail0 + lane * 16);
+    }
+#pragma unroll
+    for (int q = 0; q < PPW; ++q)
+#pragma unroll
+        for (int m = 0; m < MB; ++m) {
+            float s = acc[q][m];
+            s += __shfl_xor(s, 1, 64);
+            s += __shfl_xor(s, 2, 64);
+            s += __shfl_xor(s, 8, 64);
+            s += __shfl_xor(s, 16, 64);
+            s += __shfl_xor(s, 32, 64);
+            acc[q][m] = s;
+        }
+    if (WPP > 1) {
+        if (lane == 0 || lane == 4)
+#pragma unroll
+            for (int q = 0; q < PPW; ++q)
+#pragma unroll
+                for (int m = 0; m < MB; ++m) red[wave][q][m][col] = acc[q][m];
+        __syncthreads();
+    }
+    if (part == 0 && (lane == 0 || lane == 4)) {
+#pragma unroll
+        for (int q = 0; q < PPW; ++q) {
+            const int n = (pair0 + q) * 2 + col;
+            if (pair0 + q < npairs) {
+                const float sc = h2f(scale[n]);
+#pragma unroll
+                for (int m = 0; m < MB; ++m) {
+                    float s = acc[q][m];
+                    if (WPP > 1) {
+                        s = 0.f;
+#pragma unroll
+                        for (int w2 = 0; w2 < WPP; ++w2) s += red[wave + w2][q][m][col];
+                    }
+                    const uint16_t o = f2bf_bits(s * sc);
+                    if constexpr (BIAS) Out[(int64_t)m * N + n] = oadd_bits<true>(o, bias[n]);
+                    else Out[(int64_t)m * N + n] = o;
+                }
+            }
+        }
+    }
+}
+
+template <int MB, int PPW, bool BIAS>
+static hipError_t launch_mb_bf16(const uint16_t* A, const uint8_t* Wq, const uint16_t* scale, uint16_t* Out, int N, int K,
+                                 hipStream_t st, const uint16_t* bias)
+{
+    const int groups = (N / 2 + PPW - 1) / PPW;
+    int wpp = 1; // (launch_mb's rule)
+    while (wpp < 4 && groups * wpp < 4096 && (2 * K) / (wpp * 2) >= 2048) wpp *= 2;
+    if (wpp == 4)
+        hipLaunchKernelGGL((w8a16_gemv_bf16_kernel<MB, 4, PPW, BIAS>), dim3((unsigned)groups), dim3(256), 0, st, A, Wq, scale, Out, N, K, bias);
+    else if (wpp == 2)
+        hipLaunchKernelGGL((w8a16_gemv_bf16_kernel<MB, 2, PPW, BIAS>), dim3((unsigned)((groups + 1) / 2)), dim3(256), 0, st, A, Wq, scale,
+                           Out, N, K, bias);
+    else
+        hipLaunchKernelGGL((w8a16_gemv_bf16_kernel<MB, 1, PPW, BIAS>), dim3((unsigned)((groups + 3) / 4)), dim3(256), 0, st, A, Wq, scale,
+                           Out, N, K, bias);
+    return hipGetLastError();
+}
+
+template <bool BIAS>
+static hipError_t launch_w8a16_rows_bf16(const void* A, const uint8_t* Wq, const void* scale, void* Out, int M, int N, int K,
+                                         hipStream_t st, const uint16_t* bias)
+{
+    const uint16_t* a = static_cast<const uint16_t*>(A);
+    const uint16_t* s = static_cast<const uint16_t*>(scale);
+    uint16_t* o = static_cast<uint16_t*>(Out);
+    for (int m0 = 0; m0 < M; m0 += 4) {
+        const int mb = (M - m0) < 4 ? (M - m0) : 4;
+        hipError_t e;
+        switch (mb) {
+        case 1: e = launch_mb_bf16<1, 1, BIAS>(a + (int64_t)m0 * K, Wq, s, o + (int64_t)m0 * N, N, K, st, bias); break;
+        case 2: e = launch_mb_bf16<2, 4, BIAS>(a + (int64_t)m0 * K, Wq, s, o + (int64_t)m0 * N, N, K, st, bias); break;
+        case 3: e = launch_mb_bf16<3, 4, BIAS>(a + (int64_t)m0 * K, Wq, s, o + (int64_t)m0 * N, N, K, st, bias); break;
+        default: e = launch_mb_bf16<4, 4, BIAS>(a + (int64_t)m0 * K, Wq, s, o + (int64_t)m0 * N, N, K, st, bias); break;
+        }
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+hipError_t launch_w8a16_bf16(const void* A, const uint8_t* Wq, const void* scale, void* Out, int M, int N, int K, hipStream_t st,
+                             const void* bias)
+{
+    if (M <= 0 || N <= 0) return hipSuccess;
+    if (bias != nullptr) return launch_w8a16_rows_bf16<true>(A, Wq, scale, Out, M, N, K, st, static_cast<const uint16_t*>(bias));
+    return launch_w8a16_rows_bf16<false>(A, Wq, scale, Out, M, N, K, st, nullptr);
+}
+
 hipError_t launch_w8a16(const void* A, const uint8_t* Wq, const void* scale, void* Out, int M, int N, int K,
                         hipStream_t st, const void* bias)
 {

@@ -269,14 +269,14 @@ __global__ __launch_bounds__(WAVES_M* WAVES_N* KG * 64) void gemm_w8a8o16_kernel
     uint2 sw_pre[TN][4], bias_pre[TN][4]; // (bias_pre: EPI_DEQUANT_BIAS only, requested with the weight scales)
     if (EPI != EPI_INT32) {
 #pragma unroll
-        for (int j = 0; j < TM; ++j) sa_pre[j] = h2f(p.sA[min(m0 + wm * WM + j * 32 + lr, p.M - 1)]);
+        for (int j = 0; j < TM; ++j) sa_pre[j] = o2f<epi_bf16(EPI)>(p.sA[min(m0 + wm * WM + j * 32 + lr, p.M - 1)]);
 #pragma unroll
         for (int i = 0; i < TN; ++i)
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
                 const int nb = min(n0 + wn * WN + i * 32 + 4 * lh + 8 * g, p.N - 4);
                 sw_pre[i][g] = *reinterpret_cast<const uint2*>(p.sW + nb);
-                if constexpr (EPI == EPI_DEQUANT_BIAS) bias_pre[i][g] = *reinterpret_cast<const uint2*>(p.bias + nb);
+                if constexpr (epi_bias(EPI)) bias_pre[i][g] = *reinterpret_cast<const uint2*>(p.bias + nb);
             }
     }
 
@@ -398,7 +398,7 @@ __global__ __launch_bounds__(WAVES_M* WAVES_N* KG * 64) void gemm_w8a8o16_kernel
                     const int off = ((ks * 2 + lh) ^ sw16) << 4;
                     v8h xf = *reinterpret_cast<const v8h*>(xo + off);
                     v8h yf = *reinterpret_cast<const v8h*>(yo + off);
-                    P = __builtin_amdgcn_mfma_f32_32x32x16_f16(xf, yf, P, 0, 0, 0);
+                    P = mfma32_o<epi_bf16(EPI)>(xf, yf, P);
                 }
             }
             if (m < p.M) {
@@ -420,10 +420,11 @@ __global__ __launch_bounds__(WAVES_M* WAVES_N* KG * 64) void gemm_w8a8o16_kernel
 #pragma unroll
                         for (int e = 0; e < 4; ++e) {
                             // addend: the fp16-rounded outlier product (cuBLAS writes fp16) or the caller's y
-                            const float c = has_outliers ? h2f(f2h_bits_of_f32_result(P[4 * g + e])) : h2f(yh[e]);
+                            constexpr bool BF = epi_bf16(EPI); // (bf16 call: P and the result in bf16, no addend)
+                            const float c = has_outliers ? o2f<BF>(f2o_bits_of_f32_result<BF>(P[4 * g + e])) : h2f(yh[e]);
                             float v = __builtin_fmaf((float)acc[i][j][4 * g + e], h2f(swh[e]) * sa, c);
                             if (epi_has_silu(EPI)) v = silu_f32(v);
-                            oh[e] = f2h_bits_of_f32_result(v);
+                            oh[e] = f2o_bits_of_f32_result<BF>(v);
                         }
                         if (EPI == EPI_DEQUANT_SILU_MUL) { // gate * up: one fp16 multiply of the rounded result
                             const uint2 mb = *reinterpret_cast<const uint2*>(p.Mul + (int64_t)m * p.N + nb);
@@ -432,12 +433,12 @@ __global__ __launch_bounds__(WAVES_M* WAVES_N* KG * 64) void gemm_w8a8o16_kernel
 #pragma unroll
                             for (int e = 0; e < 4; ++e) oh[e] = f2h_bits(h2f(oh[e]) * h2f(mh[e]));
                         }
-                        if constexpr (EPI == EPI_DEQUANT_BIAS) { // the layer's bias: one fp16 add of the rounded result
+                        if constexpr (epi_bias(EPI)) { // the layer's bias: one fp16 (bf16) add of the rounded result
                             const uint2 bb = bias_pre[i][g];
                             const uint16_t bh[4] = {(uint16_t)(bb.x & 0xffffu), (uint16_t)(bb.x >> 16), (uint16_t)(bb.y & 0xffffu),
                                                     (uint16_t)(bb.y >> 16)};
 #pragma unroll
-                            for (int e = 0; e < 4; ++e) oh[e] = hadd_bits(oh[e], bh[e]);
+                            for (int e = 0; e < 4; ++e) oh[e] = oadd_bits<epi_bf16(EPI)>(oh[e], bh[e]);
                         }
                         uint2 o;
                         o.x = (unsigned)oh[0] | ((unsigned)oh[1] << 16);
@@ -641,6 +642,8 @@ hipError_t launch_gemm_deep(const GemmParams& p, int epi, hipStream_t st)
     case EPI_DEQUANT_SILU: return launch_deep_epi<EPI_DEQUANT_SILU>(p, st);
     case EPI_DEQUANT_SILU_MUL: return launch_deep_epi<EPI_DEQUANT_SILU_MUL>(p, st);
     case EPI_DEQUANT_BIAS: return launch_deep_epi<EPI_DEQUANT_BIAS>(p, st);
+    case EPI_DEQUANT_BF16: return launch_deep_epi<EPI_DEQUANT_BF16>(p, st);
+    case EPI_DEQUANT_BIAS_BF16: return launch_deep_epi<EPI_DEQUANT_BIAS_BF16>(p, st);
     default: return hipErrorInvalidValue;
     }
 }
@@ -941,7 +944,8 @@ hipError_t launch_gemm(const GemmParams& p, int epi, hipStream_t st)
     if (p.a_frag == 1 && !gemm_takes_skinny(p, epi)) return hipErrorInvalidValue; // (only the skinny kernel reads that image)
     if (p.a_frag == 2 && !(epi == EPI_DEQUANT && gemm_tp_fused_supported(p.M, p.N, p.K, p.O))) return hipErrorInvalidValue;
     if (p.a_frag < 0 || p.a_frag > 2) return hipErrorInvalidValue;
-    if (epi == EPI_DEQUANT_BIAS && (p.bias == nullptr || p.Y != nullptr)) return hipErrorInvalidValue; // (no bias form with an addend)
+    if (epi_bias(epi) && (p.bias == nullptr || p.Y != nullptr)) return hipErrorInvalidValue; // (no bias form with an addend)
+    if (epi_bf16(epi) && (p.Y != nullptr || p.O > 128)) return hipErrorInvalidValue; // (bf16 calls: enqueue's single LDS pass of outliers only)
     const int variant = gemm_variant();
     auto chose = [](const char* name) { g_last_kernel.store(name, std::memory_order_relaxed); };
     // M <= 16, and M <= 32 on narrow outputs: the weight-streaming GEMV-like kernel (measured against the split-K tiles)
@@ -981,6 +985,8 @@ hipError_t launch_gemm(const GemmParams& p, int epi, hipStream_t st)
     case EPI_DEQUANT_SILU: return launch_epi<EPI_DEQUANT_SILU>(p, st);
     case EPI_DEQUANT_SILU_MUL: return launch_epi<EPI_DEQUANT_SILU_MUL>(p, st);
     case EPI_DEQUANT_BIAS: return launch_epi<EPI_DEQUANT_BIAS>(p, st);
+    case EPI_DEQUANT_BF16: return launch_epi<EPI_DEQUANT_BF16>(p, st);
+    case EPI_DEQUANT_BIAS_BF16: return launch_epi<EPI_DEQUANT_BIAS_BF16>(p, st);
     default: return launch_epi<EPI_INT32>(p, st);
     }
 }

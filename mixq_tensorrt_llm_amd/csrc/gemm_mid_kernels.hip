@@ -87,12 +87,12 @@ __device__ __forceinline__ void mid_epi_prefetch(MidEpiPre<L::KEEP>& e, const Ge
     for (int k = 0; k < L::KEEP; ++k) {
         const HalfTile<L> t(group * L::KEEP + k);
         const int mp = min(t.m(m0, wm, lr), p.M - 1);
-        e.sa[k] = h2f(p.sA[mp]);
+        e.sa[k] = o2f<epi_bf16(EPI)>(p.sA[mp]);
 #pragma unroll
         for (int g2 = 0; g2 < 2; ++g2) {
             const int nb = min(t.n(n0, wn, lh) + 8 * g2, p.N - 4);
             e.sw[k][g2] = *reinterpret_cast<const uint2*>(p.sW + nb);
-            if constexpr (EPI == EPI_DEQUANT_BIAS) e.bias[k][g2] = *reinterpret_cast<const uint2*>(p.bias + nb);
+            if constexpr (epi_bias(EPI)) e.bias[k][g2] = *reinterpret_cast<const uint2*>(p.bias + nb);
             e.y[k][g2] = p.Y != nullptr ? *reinterpret_cast<const uint2*>(p.Y + (int64_t)mp * p.N + nb) : make_uint2(0u, 0u);
         }
     }
@@ -232,13 +232,13 @@ __device__ __forceinline__ void mid_finish(const GemmParams& p, char* smem, v16i
                     yfo[ks] = *reinterpret_cast<const v8h*>(yo + off);
                 }
 #pragma unroll
-                for (int ks = 0; ks < 8; ++ks) P = __builtin_amdgcn_mfma_f32_32x32x16_f16(xfo[ks], yfo[ks], P, 0, 0, 0);
+                for (int ks = 0; ks < 8; ++ks) P = mfma32_o<epi_bf16(EPI)>(xfo[ks], yfo[ks], P);
             } else {
                 for (int ks = 0; ks < osteps; ++ks) {
                     const int off = ((ks * 2 + lh) ^ sw16) << 4;
                     v8h xfo = *reinterpret_cast<const v8h*>(xo + off);
                     v8h yfo = *reinterpret_cast<const v8h*>(yo + off);
-                    P = __builtin_amdgcn_mfma_f32_32x32x16_f16(xfo, yfo, P, 0, 0, 0);
+                    P = mfma32_o<epi_bf16(EPI)>(xfo, yfo, P);
                 }
             }
         }
@@ -262,10 +262,10 @@ __device__ __forceinline__ void mid_finish(const GemmParams& p, char* smem, v16i
                     for (int e = 0; e < 4; ++e) {
                         // addend: the fp16-rounded outlier product (cuBLAS writes fp16) or the caller's y.  P element of (half gh, quad g2, e): 8 gh + 4 g2 + e
                         const float pe = t.gh ? P[8 + 4 * g2 + e] : P[4 * g2 + e];
-                        const float c = has_outliers ? h2f(f2h_bits_of_f32_result(pe)) : h2f(yh[e]);
+                        const float c = has_outliers ? o2f<epi_bf16(EPI)>(f2o_bits_of_f32_result<epi_bf16(EPI)>(pe)) : h2f(yh[e]);
                         float v = __builtin_fmaf((float)fin[k][4 * g2 + e], h2f(swh[e]) * sa, c);
                         if (epi_has_silu(EPI)) v = silu_f32(v);
-                        oh[e] = f2h_bits_of_f32_result(v);
+                        oh[e] = f2o_bits_of_f32_result<epi_bf16(EPI)>(v);
                     }
                     if (EPI == EPI_DEQUANT_SILU_MUL) { // gate * up: one fp16 multiply of the rounded result
                         const uint2 mb = mulq[k][g2];
@@ -274,12 +274,12 @@ __device__ __forceinline__ void mid_finish(const GemmParams& p, char* smem, v16i
 #pragma unroll
                         for (int e = 0; e < 4; ++e) oh[e] = f2h_bits(h2f(oh[e]) * h2f(mh[e]));
                     }
-                    if constexpr (EPI == EPI_DEQUANT_BIAS) { // the layer's bias: one fp16 add of the rounded result
+                    if constexpr (epi_bias(EPI)) { // the layer's bias: one fp16 (bf16) add of the rounded result
                         const uint2 bb = pre.bias[k][g2];
                         const uint16_t bh[4] = {(uint16_t)(bb.x & 0xffffu), (uint16_t)(bb.x >> 16), (uint16_t)(bb.y & 0xffffu),
                                                 (uint16_t)(bb.y >> 16)};
 #pragma unroll
-                        for (int e = 0; e < 4; ++e) oh[e] = hadd_bits(oh[e], bh[e]);
+                        for (int e = 0; e < 4; ++e) oh[e] = oadd_bits<epi_bf16(EPI)>(oh[e], bh[e]);
                     }
                     uint2 o;
                     o.x = (unsigned)oh[0] | ((unsigned)oh[1] << 16);
@@ -553,6 +553,8 @@ hipError_t launch_gemm_mid(const GemmParams& p, int epi, hipStream_t st)
     case EPI_DEQUANT_SILU: return launch_mid_epi<EPI_DEQUANT_SILU>(p, st);
     case EPI_DEQUANT_SILU_MUL: return launch_mid_epi<EPI_DEQUANT_SILU_MUL>(p, st);
     case EPI_DEQUANT_BIAS: return launch_mid_epi<EPI_DEQUANT_BIAS>(p, st);
+    case EPI_DEQUANT_BF16: return launch_mid_epi<EPI_DEQUANT_BF16>(p, st);
+    case EPI_DEQUANT_BIAS_BF16: return launch_mid_epi<EPI_DEQUANT_BIAS_BF16>(p, st);
     default: return launch_mid_epi<EPI_INT32>(p, st);
     }
 }

@@ -285,7 +285,7 @@ __global__ __launch_bounds__(512) void gemm_w8a8o16_pp128_kernel(const GemmParam
     float sa[2];
 #pragma unroll
     for (int j = 0; j < 2; ++j) // (clamped rows are never stored)
-        sa[j] = EPI == EPI_F16GEMM ? 1.f : h2f(p.sA[min(m0 + wm * 64 + j * 32 + lr, p.M - 1)]);
+        sa[j] = EPI == EPI_F16GEMM ? 1.f : o2f<epi_bf16(EPI)>(p.sA[min(m0 + wm * 64 + j * 32 + lr, p.M - 1)]);
 
     auto side = [&](int i, int j) __attribute__((always_inline)) {
         v16f P;
@@ -303,7 +303,7 @@ __global__ __launch_bounds__(512) void gemm_w8a8o16_pp128_kernel(const GemmParam
                     yf[ks] = *reinterpret_cast<const v8h*>(yo + (obase ^ ((kh * 4 + ks) << 5)));
                 }
 #pragma unroll
-                for (int ks = 0; ks < 4; ++ks) P = __builtin_amdgcn_mfma_f32_32x32x16_f16(xf[ks], yf[ks], P, 0, 0, 0);
+                for (int ks = 0; ks < 4; ++ks) P = mfma32_o<epi_bf16(EPI)>(xf[ks], yf[ks], P);
             }
         }
         return P;
@@ -316,8 +316,8 @@ __global__ __launch_bounds__(512) void gemm_w8a8o16_pp128_kernel(const GemmParam
         for (int g = 0; g < 4; ++g)
             swq[i][g] = EPI == EPI_F16GEMM ? make_uint2(0u, 0u)
                                            : *reinterpret_cast<const uint2*>(p.sW + min(n0 + wn * 64 + i * 32 + 4 * lh + 8 * g, p.N - 4));
-    uint2 bq[2][4]; // (EPI_DEQUANT_BIAS) the layer's bias of the same column quads, requested with the weight scales
-    if constexpr (EPI == EPI_DEQUANT_BIAS) {
+    uint2 bq[2][4]; // (EPI_DEQUANT_BIAS, _BF16) the layer's bias of the same column quads, requested with the weight scales
+    if constexpr (epi_bias(EPI)) {
 #pragma unroll
         for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -375,7 +375,10 @@ __global__ __launch_bounds__(512) void gemm_w8a8o16_pp128_kernel(const GemmParam
             for (int e2 = 0; e2 < 4; e2 += 2) {
                 const v2f s2 = v2f{swf[e2], swf[e2 + 1]} * sa[j]; // exact: fp16 x fp16 products
                 v2f c2;
-                if (HAS_O) {
+                if (HAS_O && epi_bf16(EPI)) { // (bf16 call) the product rounded to bf16
+                    const unsigned pb = __builtin_bit_cast(unsigned, f2bf2_of_f32_results(P[4 * g + e2], P[4 * g + e2 + 1]));
+                    c2 = v2f{bf2f((uint16_t)(pb & 0xffffu)), bf2f((uint16_t)(pb >> 16))};
+                } else if (HAS_O) {
                     const v2h p16 = f2h2(P[4 * g + e2], P[4 * g + e2 + 1]); // MFMA outputs: nothing to fuse with
                     c2 = v2f{(float)p16[0], (float)p16[1]};
                 } else {
@@ -394,9 +397,10 @@ __global__ __launch_bounds__(512) void gemm_w8a8o16_pp128_kernel(const GemmParam
                     v0 = silu_f32(v0);
                     v1 = silu_f32(v1);
                 }
-                v2h o16 = f2h2_of_f32_results(v0, v1);
+                v2h o16 = f2o2_of_f32_results<epi_bf16(EPI)>(v0, v1);
                 if (EPI == EPI_DEQUANT_SILU_MUL) o16 = o16 * __builtin_bit_cast(v2h, e2 ? mulq.y : mulq.x); // gate * up
                 if constexpr (EPI == EPI_DEQUANT_BIAS) o16 = o16 + __builtin_bit_cast(v2h, e2 ? bq[i][g].y : bq[i][g].x); // + bias (fp16 add)
+                if constexpr (EPI == EPI_DEQUANT_BIAS_BF16) o16 = bf2_add(o16, e2 ? bq[i][g].y : bq[i][g].x); // + bias (bf16 add)
                 __builtin_memcpy(&ow[e2 >> 1], &o16, 4);
             }
             const int c = i * 4 + g; // 16-byte chunk of the 128-byte row
@@ -463,8 +467,8 @@ template <int EPI>
 static hipError_t launch_pp128_epi(const GemmParams& p, hipStream_t st)
 {
     if (p.O > 0) return launch_pp128_cfg<EPI, true, false>(p, st); // the API never passes both an addend and outliers
-    if constexpr (EPI == EPI_DEQUANT_BIAS) {
-        if (p.Y != nullptr) return hipErrorInvalidValue; // (the bias epilogue takes no addend)
+    if constexpr (epi_bias(EPI) || epi_bf16(EPI)) {
+        if (p.Y != nullptr) return hipErrorInvalidValue; // (the bias and bf16 epilogues take no addend)
     } else if (p.Y != nullptr) return launch_pp128_cfg<EPI, false, true>(p, st);
     return launch_pp128_cfg<EPI, false, false>(p, st);
 }
@@ -486,6 +490,8 @@ hipError_t launch_gemm_pp128(const GemmParams& p, int epi, hipStream_t st)
     case EPI_DEQUANT_SILU: return launch_pp128_epi<EPI_DEQUANT_SILU>(p, st);
     case EPI_DEQUANT_SILU_MUL: return launch_pp128_epi<EPI_DEQUANT_SILU_MUL>(p, st);
     case EPI_DEQUANT_BIAS: return launch_pp128_epi<EPI_DEQUANT_BIAS>(p, st);
+    case EPI_DEQUANT_BF16: return launch_pp128_epi<EPI_DEQUANT_BF16>(p, st);
+    case EPI_DEQUANT_BIAS_BF16: return launch_pp128_epi<EPI_DEQUANT_BIAS_BF16>(p, st);
     default: return launch_pp128_cfg<EPI_INT32, false, false>(p, st);
     }
 }

@@ -109,6 +109,8 @@ __global__ __launch_bounds__(512) void gemm_w8a8o16_pp_kernel(const GemmParams p
     static_assert(!TP || (SPLITK == 0 && (EPI == EPI_DEQUANT || EPI == EPI_DEQUANT_BIAS) && ABL == 0),
                   "the peer-write epilogue exists for the plain kernel");
     static_assert(EPI != EPI_DEQUANT_BIAS || (!HAS_Y && ABL == 0), "the bias epilogue takes no addend y");
+    static_assert(!epi_bf16(EPI) || (!HAS_Y && ABL == 0 && !TP), "the bf16 epilogues take no addend y and no peer writes");
+    constexpr bool BF = epi_bf16(EPI); // (bf16 call: sA, the outlier operands, P and D in bf16)
     constexpr int S = SPLITK ? SPLITK : 1; // workgroups per tile
     constexpr int PJ = S >= 4 ? 1 : 4 / S; // 32-row m tiles (per wave) this workgroup finishes
     constexpr int NI = S == 8 ? 1 : 2;     // 32-column n tiles (per wave) it finishes: S = 8 splits the n pair as well
@@ -592,7 +594,7 @@ __global__ __launch_bounds__(512) void gemm_w8a8o16_pp_kernel(const GemmParams p
                     yf[ks] = *reinterpret_cast<const v8h*>(yo + (obase ^ ((kh * 4 + ks) << 5)));
                 }
 #pragma unroll
-                for (int ks = 0; ks < 4; ++ks) P = __builtin_amdgcn_mfma_f32_32x32x16_f16(xf[ks], yf[ks], P, 0, 0, 0);
+                for (int ks = 0; ks < 4; ++ks) P = mfma32_o<BF>(xf[ks], yf[ks], P);
             }
         }
         return P;
@@ -649,7 +651,7 @@ __global__ __launch_bounds__(512) void gemm_w8a8o16_pp_kernel(const GemmParams p
     // dequant of tile (i, j) with its side product P -> 4 quads (4 consecutive n of row m each) -> window
     auto dequant = [&](int i, int j, const v16f& P) __attribute__((always_inline)) {
         uint2 bq[4];
-        if constexpr (EPI == EPI_DEQUANT_BIAS) {
+        if constexpr (epi_bias(EPI)) {
             int bcol = n0 + wn * 64 + imap(i) * 32 + 4 * lh;
             asm volatile("" : "+v"(bcol));
 #pragma unroll
@@ -673,7 +675,10 @@ __global__ __launch_bounds__(512) void gemm_w8a8o16_pp_kernel(const GemmParams p
                 const v2f s2 = v2f{swf[e2], swf[e2 + 1]} * sa_cur; // exact: fp16 x fp16 products
                 // addend pair: the fp16-rounded outlier products (cuBLAS writes fp16) or the caller's y
                 v2f c2;
-                if (HAS_O) {
+                if (HAS_O && BF) { // (bf16 call) the product rounded to bf16
+                    const unsigned pb = __builtin_bit_cast(unsigned, f2bf2_of_f32_results(P[4 * g + e2], P[4 * g + e2 + 1]));
+                    c2 = v2f{bf2f((uint16_t)(pb & 0xffffu)), bf2f((uint16_t)(pb >> 16))};
+                } else if (HAS_O) {
                     const v2h p16 = f2h2(P[4 * g + e2], P[4 * g + e2 + 1]); // MFMA outputs: nothing to fuse with
                     c2 = v2f{(float)p16[0], (float)p16[1]};
                 } else {
@@ -693,9 +698,10 @@ __global__ __launch_bounds__(512) void gemm_w8a8o16_pp_kernel(const GemmParams p
                     v0 = silu_f32(v0);
                     v1 = silu_f32(v1);
                 }
-                v2h o16 = f2h2_of_f32_results(v0, v1);
+                v2h o16 = f2o2_of_f32_results<BF>(v0, v1);
                 if (EPI == EPI_DEQUANT_SILU_MUL) o16 = o16 * __builtin_bit_cast(v2h, e2 ? mulq.y : mulq.x); // gate * up
                 if constexpr (EPI == EPI_DEQUANT_BIAS) o16 = o16 + __builtin_bit_cast(v2h, e2 ? bq[g].y : bq[g].x); // + bias (fp16 add)
+                if constexpr (EPI == EPI_DEQUANT_BIAS_BF16) o16 = bf2_add(o16, e2 ? bq[g].y : bq[g].x); // + bias (bf16 add)
                 __builtin_memcpy(&ow[e2 >> 1], &o16, 4);
             }
             if (S == 8) { // a single 32x32 tile per wave: 8-byte stores straight from the accumulator layout
@@ -763,7 +769,7 @@ __global__ __launch_bounds__(512) void gemm_w8a8o16_pp_kernel(const GemmParams p
             v16f Pnext = Pcur;
             if (t + 1 < nt) Pnext = side((t + 1) & 1, (t + 1) >> 1);
             if (EPI != EPI_F16GEMM && (t & 1) == 0) { // block j = t >> 1 starts: its row scale arrives, the next one is requested
-                sa_cur = h2f(sa_next);
+                sa_cur = o2f<BF>(sa_next);
                 if (t + 2 < nt) sa_next = load_sa((t >> 1) + 1);
             }
             if ((HAS_Y || HAS_MUL) && (t & 1) == 0) { // block j = t >> 1 starts: operands of this block -> registers
@@ -905,7 +911,7 @@ static hipError_t launch_pp_epi(const GemmParams& p, hipStream_t st)
 {
     const bool has_o = p.O > 0, has_y = p.Y != nullptr;
     if (has_o) return launch_pp_cfg<EPI, true, false>(p, st); // the API never passes both an addend and outliers
-    if constexpr (EPI == EPI_DEQUANT_BIAS) {
+    if constexpr (epi_bias(EPI) || epi_bf16(EPI)) {
         if (has_y) return hipErrorInvalidValue;
     } else if (has_y) return launch_pp_cfg<EPI, false, true>(p, st);
     return launch_pp_cfg<EPI, false, false>(p, st);
@@ -1051,7 +1057,7 @@ template <int EPI, int SPLITK>
 static hipError_t launch_pp_splitk_epi(const GemmParams& p, hipStream_t st)
 {
     if (p.O > 0) return launch_pp_splitk_cfg<EPI, true, false, SPLITK>(p, st);
-    if constexpr (EPI == EPI_DEQUANT_BIAS) {
+    if constexpr (epi_bias(EPI) || epi_bf16(EPI)) {
         if (p.Y != nullptr) return hipErrorInvalidValue;
     } else if (p.Y != nullptr) return launch_pp_splitk_cfg<EPI, false, true, SPLITK>(p, st);
     return launch_pp_splitk_cfg<EPI, false, false, SPLITK>(p, st);
@@ -1082,6 +1088,14 @@ hipError_t launch_gemm_pp_splitk(const GemmParams& p_in, int epi, hipStream_t st
         return s == 8   ? launch_pp_splitk_epi<EPI_DEQUANT_BIAS, 8>(p, st)
                : s == 4 ? launch_pp_splitk_epi<EPI_DEQUANT_BIAS, 4>(p, st)
                         : launch_pp_splitk_epi<EPI_DEQUANT_BIAS, 2>(p, st);
+    case EPI_DEQUANT_BF16:
+        return s == 8   ? launch_pp_splitk_epi<EPI_DEQUANT_BF16, 8>(p, st)
+               : s == 4 ? launch_pp_splitk_epi<EPI_DEQUANT_BF16, 4>(p, st)
+                        : launch_pp_splitk_epi<EPI_DEQUANT_BF16, 2>(p, st);
+    case EPI_DEQUANT_BIAS_BF16:
+        return s == 8   ? launch_pp_splitk_epi<EPI_DEQUANT_BIAS_BF16, 8>(p, st)
+               : s == 4 ? launch_pp_splitk_epi<EPI_DEQUANT_BIAS_BF16, 4>(p, st)
+                        : launch_pp_splitk_epi<EPI_DEQUANT_BIAS_BF16, 2>(p, st);
     default: return hipErrorInvalidValue;
     }
 }
@@ -1114,6 +1128,8 @@ hipError_t launch_gemm_pp(const GemmParams& p, int epi, hipStream_t st)
     case EPI_DEQUANT_SILU: return launch_pp_epi<EPI_DEQUANT_SILU>(p, st);
     case EPI_DEQUANT_SILU_MUL: return launch_pp_epi<EPI_DEQUANT_SILU_MUL>(p, st);
     case EPI_DEQUANT_BIAS: return launch_pp_epi<EPI_DEQUANT_BIAS>(p, st);
+    case EPI_DEQUANT_BF16: return launch_pp_epi<EPI_DEQUANT_BF16>(p, st);
+    case EPI_DEQUANT_BIAS_BF16: return launch_pp_epi<EPI_DEQUANT_BIAS_BF16>(p, st);
     default: return launch_pp_cfg<EPI_INT32, false, false>(p, st);
     }
 }

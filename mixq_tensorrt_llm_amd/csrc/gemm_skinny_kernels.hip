@@ -254,7 +254,7 @@ __global__ __launch_bounds__(KW * 64) void gemm_skinny_kernel(const GemmParams p
             if (tt == wave) { // (the wave's first tile) the first PRE steps were requested before the main loop
 #pragma unroll
                 for (int u = 0; u < PRE; ++u)
-                    if (u * 64 < obytes) P = __builtin_amdgcn_mfma_f32_16x16x32_f16(pxf[u], pyf[u], P, 0, 0, 0);
+                    if (u * 64 < obytes) P = mfma16_o<epi_bf16(EPI)>(pxf[u], pyf[u], P);
             }
             for (int k0 = (tt == wave ? PRE * 64 : 0); k0 < obytes; k0 += 64) { // 32 outlier columns per step, 8 per lane
                 const int kb = k0 + lq * 16;
@@ -266,11 +266,11 @@ __global__ __launch_bounds__(KW * 64) void gemm_skinny_kernel(const GemmParams p
 #pragma unroll
                     for (int e = 0; e < 8; ++e) xf[e] = (_Float16)0.f, yf[e] = (_Float16)0.f;
                 }
-                P = __builtin_amdgcn_mfma_f32_16x16x32_f16(xf, yf, P, 0, 0, 0);
+                P = mfma16_o<epi_bf16(EPI)>(xf, yf, P);
             }
         }
         if (m < p.M && nb < p.N) {
-            const float sa = h2f(tt == wave ? psa : p.sA[m]);
+            const float sa = o2f<epi_bf16(EPI)>(tt == wave ? psa : p.sA[m]);
             const uint2 swb = tt == wave ? psw : *reinterpret_cast<const uint2*>(p.sW + nb);
             const uint16_t swh[4] = {(uint16_t)(swb.x & 0xffffu), (uint16_t)(swb.x >> 16), (uint16_t)(swb.y & 0xffffu),
                                      (uint16_t)(swb.y >> 16)};
@@ -283,10 +283,10 @@ __global__ __launch_bounds__(KW * 64) void gemm_skinny_kernel(const GemmParams p
             uint16_t oh[4];
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-                const float c = p.O > 0 ? h2f(f2h_bits_of_f32_result(P[e])) : h2f(yh[e]);
+                const float c = p.O > 0 ? o2f<epi_bf16(EPI)>(f2o_bits_of_f32_result<epi_bf16(EPI)>(P[e])) : h2f(yh[e]);
                 float v = __builtin_fmaf((float)a[e], h2f(swh[e]) * sa, c);
                 if (epi_has_silu(EPI)) v = silu_f32(v);
-                oh[e] = f2h_bits_of_f32_result(v);
+                oh[e] = f2o_bits_of_f32_result<epi_bf16(EPI)>(v);
             }
             if (EPI == EPI_DEQUANT_SILU_MUL) { // gate * up
                 const uint2 mb = *reinterpret_cast<const uint2*>(p.Mul + (int64_t)m * p.N + nb);
@@ -295,14 +295,14 @@ __global__ __launch_bounds__(KW * 64) void gemm_skinny_kernel(const GemmParams p
 #pragma unroll
                 for (int e = 0; e < 4; ++e) oh[e] = f2h_bits(h2f(oh[e]) * h2f(mh[e]));
             }
-            if constexpr (EPI == EPI_DEQUANT_BIAS) { // the layer's bias: one fp16 add of the rounded result
+            if constexpr (epi_bias(EPI)) { // the layer's bias: one fp16 (bf16) add of the rounded result
                 // (requested here, not with psw at kernel start: two registers more through the main loop cost the 17..32-row forms
                 //  half their occupancy -- 240 + 16 -> 242 + 16 of 256 registers)
                 const uint2 bb = *reinterpret_cast<const uint2*>(p.bias + nb);
                 const uint16_t bh[4] = {(uint16_t)(bb.x & 0xffffu), (uint16_t)(bb.x >> 16), (uint16_t)(bb.y & 0xffffu),
                                         (uint16_t)(bb.y >> 16)};
 #pragma unroll
-                for (int e = 0; e < 4; ++e) oh[e] = hadd_bits(oh[e], bh[e]);
+                for (int e = 0; e < 4; ++e) oh[e] = oadd_bits<epi_bf16(EPI)>(oh[e], bh[e]);
             }
             uint2 o;
             o.x = (unsigned)oh[0] | ((unsigned)oh[1] << 16);
@@ -714,6 +714,8 @@ hipError_t launch_gemm_skinny(const GemmParams& p, int epi, hipStream_t st)
     case EPI_DEQUANT_SILU: return launch_skinny_epi<EPI_DEQUANT_SILU>(p, st);
     case EPI_DEQUANT_SILU_MUL: return launch_skinny_epi<EPI_DEQUANT_SILU_MUL>(p, st);
     case EPI_DEQUANT_BIAS: return launch_skinny_epi<EPI_DEQUANT_BIAS>(p, st);
+    case EPI_DEQUANT_BF16: return launch_skinny_epi<EPI_DEQUANT_BF16>(p, st);
+    case EPI_DEQUANT_BIAS_BF16: return launch_skinny_epi<EPI_DEQUANT_BIAS_BF16>(p, st);
     default: return launch_skinny_epi<EPI_INT32>(p, st);
     }
 }

@@ -9,6 +9,7 @@
 #include <cstdlib>
 #include <cstdio>
 #include <cstring>
+#include <map>
 #include <mutex>
 #include <new>
 #include <string>
@@ -165,7 +166,19 @@ void mixq_debug_reset(void)
     mixq::set_s4_wrows(1);
 }
 
-const char* mixq_debug_last_gemm_kernel(void) { return mixq::last_gemm_kernel(); }
+static std::atomic<bool> g_last_gemm_bf16{false}; // reporting only: the last fused GEMM was a bf16 call's
+// (a bf16 call: the family's name + " [bf16]", interned once per family)
+const char* mixq_debug_last_gemm_kernel(void)
+{
+    const char* k = mixq::last_gemm_kernel();
+    if (!g_last_gemm_bf16.load(std::memory_order_relaxed)) return k;
+    static std::mutex mu;
+    static std::map<std::string, std::string> names;
+    std::lock_guard<std::mutex> lock(mu);
+    auto it = names.find(k);
+    if (it == names.end()) it = names.emplace(k, std::string(k) + " [bf16]").first;
+    return it->second.c_str();
+}
 const char* mixq_debug_last_producer_kernel(void) { return mixq::last_producer_kernel(); }
 
 const char* mixq_version(void) { return "mixq-mi355x 0.3 (gfx950)"; }
@@ -181,6 +194,7 @@ const char* mixq_error_string(int code)
     case MIXQ_E_HIP: return "HIP error";
     case MIXQ_E_WORKSPACE: return "workspace missing";
     case MIXQ_E_STALE: return "registered weight image does not match the weight's current content";
+    case MIXQ_E_TYPE: return "descriptor types are not a supported combination";
     default: return "unknown";
     }
 }
@@ -300,10 +314,19 @@ int mixq_supports_format_combination(const mixq_handle*, int pos, const mixq_ten
                                      int nbOutputs)
 {
     if (!inOut || pos < 0 || pos >= nbInputs + nbOutputs || pos > 7) return 0;
-    return (inOut[pos].type == MIXQ_TYPE_HALF && inOut[pos].format == MIXQ_FORMAT_LINEAR) ? 1 : 0;
+    if (inOut[pos].format != MIXQ_FORMAT_LINEAR) return 0;
+    const int t = inOut[pos].type;
+    if (pos == 0) return (t == MIXQ_TYPE_HALF || t == MIXQ_TYPE_BF16) ? 1 : 0; // bf16 calls (MI355X extension)
+    if (pos == 3 || pos == 7) return t == inOut[0].type && (t == MIXQ_TYPE_HALF || t == MIXQ_TYPE_BF16) ? 1 : 0;
+    return t == MIXQ_TYPE_HALF ? 1 : 0;
 }
 
 int mixq_get_output_data_type(const mixq_handle*, int) { return MIXQ_TYPE_HALF; }
+
+int mixq_get_output_data_type_for(const mixq_handle*, int, const int32_t* inputTypes, int nbInputs)
+{
+    return inputTypes && nbInputs >= 1 && inputTypes[0] == MIXQ_TYPE_BF16 ? MIXQ_TYPE_BF16 : MIXQ_TYPE_HALF;
+}
 
 // ------------------------------------------------------------------------------------------ workspace ---
 // Bytes of the qA region of the workspace carve for a call with M rows: M x K row-major -- or, for decode batches, room for the
@@ -679,7 +702,8 @@ int mixq_gemm_mixed(const int8_t* qA, const int8_t* W, const void* sA, const voi
 
 static int gemm_mixed_impl(const int8_t* qA, const int8_t* W, const void* sA, const void* sW, const void* fpA, const void* fpW,
                            void* Out, int M, int N, int K, int O, void* scratch, size_t scratch_bytes, void* stream,
-                           int a_frag, const void* b_image = nullptr, bool image_resolved = false, const void* bias = nullptr);
+                           int a_frag, const void* b_image = nullptr, bool image_resolved = false, const void* bias = nullptr,
+                           bool bf16 = false);
 
 int mixq_gemm_mixed_scratch(const int8_t* qA, const int8_t* W, const void* sA, const void* sW, const void* fpA,
                             const void* fpW, void* Out, int M, int N, int K, int O, void* scratch, size_t scratch_bytes,
@@ -703,7 +727,7 @@ int mixq_gemm_mixed_bias(const int8_t* qA, const int8_t* W, const void* sA, cons
 // bias: the layer's fp16 [N] bias (EPI_DEQUANT_BIAS: the same kernel as EPI_DEQUANT, one fp16 add in its epilogue), or null
 static int gemm_mixed_impl(const int8_t* qA, const int8_t* W, const void* sA, const void* sW, const void* fpA, const void* fpW,
                            void* Out, int M, int N, int K, int O, void* scratch, size_t scratch_bytes, void* stream,
-                           int a_frag, const void* b_image, bool image_resolved, const void* bias)
+                           int a_frag, const void* b_image, bool image_resolved, const void* bias, bool bf16)
 {
     if (M < 0 || N < 0 || K <= 0 || O < 0) return MIXQ_E_BADARG;
     if (M == 0 || N == 0) return MIXQ_OK;
@@ -726,9 +750,12 @@ static int gemm_mixed_impl(const int8_t* qA, const int8_t* W, const void* sA, co
     if (O <= kNumOutliers) {
         p.fpA = static_cast<const uint16_t*>(fpA), p.fpW = static_cast<const uint16_t*>(fpW), p.O = O;
         p.bias = static_cast<const uint16_t*>(bias);
-        return hip_rc(mixq::launch_gemm(p, bias ? mixq::EPI_DEQUANT_BIAS : mixq::EPI_DEQUANT, st));
+        const int epi = bf16 ? (bias ? mixq::EPI_DEQUANT_BIAS_BF16 : mixq::EPI_DEQUANT_BF16)
+                             : (bias ? mixq::EPI_DEQUANT_BIAS : mixq::EPI_DEQUANT);
+        g_last_gemm_bf16.store(bf16, std::memory_order_relaxed);
+        return hip_rc(mixq::launch_gemm(p, epi, st));
     }
-    if (bias) return MIXQ_E_SHAPE;
+    if (bias || bf16) return MIXQ_E_SHAPE;
     // more outlier columns than one LDS pass holds: the reference's own two-step order (side GEMM into Out, then C = D = Out)
     hipError_t e = mixq::launch_gemm_fp16(fpA, fpW, Out, M, N, O, st);
     if (e != hipSuccess) return MIXQ_E_HIP;
@@ -958,9 +985,12 @@ static int enqueue_qa_frag(int64_t M, int64_t N, int64_t K, void* scratch, const
 
 static int enqueue_impl(const mixq_handle* h, const mixq_tensor_desc* inputDesc, const void* const* inputs,
                         void* const* outputs, void* workspace, void* stream, void* ev_gemm_start, void* ev_gemm_stop,
-                        const void* bias = nullptr)
+                        const void* bias = nullptr, const mixq_tensor_desc* outputDesc = nullptr)
 {
     if (!h || !inputDesc || !inputs || !outputs) return MIXQ_E_BADARG;
+    // bf16 call: A, fp_weight, the output and the bias are bf16 (include/mixq.h); any other type of A is the fp16 call
+    const bool bf16 = inputDesc[0].type == MIXQ_TYPE_BF16;
+    if (bf16 && (inputDesc[3].type != MIXQ_TYPE_BF16 || (outputDesc && outputDesc[0].type != MIXQ_TYPE_BF16))) return MIXQ_E_TYPE;
     const mixq_tensor_desc& a = inputDesc[0];
     if (a.nbDims < 1 || a.nbDims > MIXQ_MAX_DIMS || inputDesc[1].nbDims < 1) return MIXQ_E_BADARG;
     int64_t M = 1;
@@ -1016,13 +1046,22 @@ static int enqueue_impl(const mixq_handle* h, const mixq_tensor_desc* inputDesc,
         const void* img = M <= 64 ? mixq::resolve_weight_image(W, (int)N, (int)K, st) : nullptr; // (ONE lookup per call: probe and launch agree)
         const int frag = enqueue_qa_frag(M, N, K, scratch, W, img);
         int rc = hip_rc(mixq::launch_quant_extract(const_cast<void*>(A), qA, sA, fpA, ind, (int)M, (int)K, kNumOutliers,
-                                                   false, st, scratch, frag));
+                                                   false, st, scratch, frag, bf16));
         if (rc != MIXQ_OK) return rc;
         if (ev_gemm_start && hipEventRecord(static_cast<hipEvent_t>(ev_gemm_start), st) != hipSuccess) return MIXQ_E_HIP;
         rc = gemm_mixed_impl(qA, W, sA, scale_b, fpA, fp_weight, Out, (int)M, (int)N, (int)K, kNumOutliers, scratch,
-                             scratch_bytes, stream, frag, img, true, bias);
+                             scratch_bytes, stream, frag, img, true, bias, bf16);
         if (ev_gemm_stop && hipEventRecord(static_cast<hipEvent_t>(ev_gemm_stop), st) != hipSuccess) return MIXQ_E_HIP;
         return rc;
+    }
+    if (bf16) { // M <= 4 of a bf16 call: the same two forms as the fp16 call (the GEMV / the fpA_intB skinny form), bf16 twins
+        if (K % 64 || N % 2) return MIXQ_E_SHAPE;
+        if (!aligned16(A) || !aligned16(q_weight)) return MIXQ_E_ALIGN;
+        hipStream_t st = static_cast<hipStream_t>(stream);
+        if (!mixq::w8a16_skinny_takes((int)M, (int)N, (int)K))
+            return hip_rc(mixq::launch_w8a16_bf16(A, q_weight, scaling_factors, Out, (int)M, (int)N, (int)K, st, bias));
+        if (K % 8 || (reinterpret_cast<uintptr_t>(Out) & 3u)) return MIXQ_E_ALIGN;
+        return hip_rc(mixq::launch_w8a16_skinny_bf16(A, q_weight, scaling_factors, Out, (int)M, (int)N, (int)K, bias, st));
     }
     if (!bias) return mixq_w8a16_gemm_forward(A, q_weight, scaling_factors, Out, (int)M, (int)N, (int)K, stream);
     // M <= 4 with the bias: the same two forms mixq_w8a16_gemm_forward picks from (the GEMV / the fpA_intB skinny form)
@@ -1057,24 +1096,24 @@ int mixq_describe_plan(int64_t M, int64_t N, int64_t K, int have_weight_image, c
     return MIXQ_OK;
 }
 
-int mixq_enqueue(const mixq_handle* h, const mixq_tensor_desc* inputDesc, const mixq_tensor_desc* /*outputDesc*/,
+int mixq_enqueue(const mixq_handle* h, const mixq_tensor_desc* inputDesc, const mixq_tensor_desc* outputDesc,
                  const void* const* inputs, void* const* outputs, void* workspace, void* stream)
 {
-    return enqueue_impl(h, inputDesc, inputs, outputs, workspace, stream, nullptr, nullptr);
+    return enqueue_impl(h, inputDesc, inputs, outputs, workspace, stream, nullptr, nullptr, nullptr, outputDesc);
 }
 
-int mixq_enqueue_bias(const mixq_handle* h, const mixq_tensor_desc* inputDesc, const mixq_tensor_desc* /*outputDesc*/,
+int mixq_enqueue_bias(const mixq_handle* h, const mixq_tensor_desc* inputDesc, const mixq_tensor_desc* outputDesc,
                       const void* const* inputs, void* const* outputs, const void* bias_f16, void* workspace, void* stream)
 {
     if (bias_f16 && !aligned16(bias_f16)) return MIXQ_E_ALIGN;
-    return enqueue_impl(h, inputDesc, inputs, outputs, workspace, stream, nullptr, nullptr, bias_f16);
+    return enqueue_impl(h, inputDesc, inputs, outputs, workspace, stream, nullptr, nullptr, bias_f16, outputDesc);
 }
 
 int mixq_enqueue_profiled(const mixq_handle* h, const mixq_tensor_desc* inputDesc,
-                          const mixq_tensor_desc* /*outputDesc*/, const void* const* inputs, void* const* outputs,
+                          const mixq_tensor_desc* outputDesc, const void* const* inputs, void* const* outputs,
                           void* workspace, void* stream, void* ev_gemm_start, void* ev_gemm_stop)
 {
-    return enqueue_impl(h, inputDesc, inputs, outputs, workspace, stream, ev_gemm_start, ev_gemm_stop);
+    return enqueue_impl(h, inputDesc, inputs, outputs, workspace, stream, ev_gemm_start, ev_gemm_stop, nullptr, outputDesc);
 }
 
 // ------------------------------------------------------------------------------ multi-GPU ----
@@ -1090,6 +1129,7 @@ static int enqueue_tp_impl(const mixq_handle* h, const mixq_tensor_desc* inputDe
                            void* workspace, const mixq_tp_epilogue* tp, void* stream)
 {
     if (!h || !inputDesc || !inputs || !tp) return MIXQ_E_BADARG;
+    if (inputDesc[0].type == MIXQ_TYPE_BF16) return MIXQ_E_TYPE; // (the fused all-gather is fp16 only)
     const mixq_tensor_desc& a = inputDesc[0];
     if (a.nbDims < 1 || a.nbDims > MIXQ_MAX_DIMS || inputDesc[1].nbDims < 1) return MIXQ_E_BADARG;
     int64_t M = 1;

@@ -51,6 +51,42 @@ __device__ __forceinline__ uint16_t f2h_bits(float f)
 // torch's fp16 add) -- fp32 carries more than 2 x 11 + 2 bits, so the double rounding is innocuous.
 __device__ __forceinline__ uint16_t hadd_bits(uint16_t a, uint16_t b) { return f2h_bits(h2f(a) + h2f(b)); }
 
+// ---- bf16 operands of a bf16 call (EPI_DEQUANT_BF16 / EPI_DEQUANT_BIAS_BF16): BF selects the 16-bit activation / output type ----
+typedef __bf16 v8bf __attribute__((ext_vector_type(8)));
+typedef __bf16 v2bf __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ float bf2f(uint16_t bits) { return __builtin_bit_cast(float, (unsigned)bits << 16); }
+__device__ __forceinline__ uint16_t f2bf_bits(float f) // v_cvt_pk_bf16_f32, round-to-nearest-even
+{
+    return __builtin_bit_cast(uint16_t, (__bf16)f);
+}
+// a 16-bit activation / output value -> fp32
+template <bool BF>
+__device__ __forceinline__ float o2f(uint16_t bits)
+{
+    if constexpr (BF) return bf2f(bits);
+    else return h2f(bits);
+}
+// outlier product step: D += x y^T on the fp16 or the bf16 MFMA (same lane maps, same C/D layout)
+template <bool BF>
+__device__ __forceinline__ v16f mfma32_o(v8h x, v8h y, v16f c)
+{
+    if constexpr (BF) return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(v8bf, x), __builtin_bit_cast(v8bf, y), c, 0, 0, 0);
+    else return __builtin_amdgcn_mfma_f32_32x32x16_f16(x, y, c, 0, 0, 0);
+}
+template <bool BF>
+__device__ __forceinline__ v4f mfma16_o(v8h x, v8h y, v4f c)
+{
+    if constexpr (BF) return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(v8bf, x), __builtin_bit_cast(v8bf, y), c, 0, 0, 0);
+    else return __builtin_amdgcn_mfma_f32_16x16x32_f16(x, y, c, 0, 0, 0);
+}
+
+// bytes b0, b1 of an interleaved qweight word -> packed bf16 pair (byte - 128): exact, |byte - 128| <= 128 (bf16 calls, M <= 4)
+__device__ __forceinline__ unsigned wpair_bf16(unsigned w, int b0, int b1)
+{
+    const float f0 = (float)(int)((w >> (8 * b0)) & 0xffu) - 128.f, f1 = (float)(int)((w >> (8 * b1)) & 0xffu) - 128.f;
+    return __builtin_amdgcn_perm(__builtin_bit_cast(unsigned, f1), __builtin_bit_cast(unsigned, f0), 0x07060302u);
+}
+
 // SiLU as the reference writes it (linear_combination_dequant.h:167-170, cult.cu:2301-2304): x / (1 + expf(-x)) with the
 // accurate library expf (<= 1 ulp, like CUDA's expf without -use_fast_math) and an IEEE division -- not the
 // hardware v_exp_f32 approximation (__expf).
@@ -65,12 +101,47 @@ __device__ __forceinline__ uint16_t f2h_bits_of_f32_result(float f)
     return f2h_bits(f);
 }
 
+// fp32 result -> fp16 (pinned, as above) or bf16 (RNE)
+template <bool BF>
+__device__ __forceinline__ uint16_t f2o_bits_of_f32_result(float f)
+{
+    if constexpr (BF) return f2bf_bits(f);
+    else return f2h_bits_of_f32_result(f);
+}
+// 16-bit + 16-bit of the output type, rounded once (the bias add; bf16: the fp32 sum of two bf16 is exact below 2^-133 .. 2^128
+// spans except for its single rounding, so bf16(fp32 sum) is the correctly rounded bf16 sum)
+template <bool BF>
+__device__ __forceinline__ uint16_t oadd_bits(uint16_t a, uint16_t b)
+{
+    if constexpr (BF) return f2bf_bits(bf2f(a) + bf2f(b));
+    else return hadd_bits(a, b);
+}
+
 // Two fp32 results -> packed fp16 (RNE), both pinned first (same reason); one v_cvt_pk_f16_f32.
 __device__ __forceinline__ v2h f2h2_of_f32_results(float a, float b)
 {
     asm("" : "+v"(a), "+v"(b));
     typedef float v2f_ __attribute__((ext_vector_type(2)));
     return __builtin_convertvector(v2f_{a, b}, v2h);
+}
+
+// The same for bf16 (one v_cvt_pk_bf16_f32), as the bits of a v2h so that the fp16 code paths can carry it
+__device__ __forceinline__ v2h f2bf2_of_f32_results(float a, float b)
+{
+    typedef float v2f_ __attribute__((ext_vector_type(2)));
+    return __builtin_bit_cast(v2h, __builtin_convertvector(v2f_{a, b}, v2bf));
+}
+// a packed bf16 pair + the bf16 pair b, each rounded once (the bias add of the packed epilogues)
+__device__ __forceinline__ v2h bf2_add(v2h a, unsigned b)
+{
+    const unsigned u = __builtin_bit_cast(unsigned, a);
+    return f2bf2_of_f32_results(bf2f((uint16_t)(u & 0xffffu)) + bf2f((uint16_t)(b & 0xffffu)), bf2f((uint16_t)(u >> 16)) + bf2f((uint16_t)(b >> 16)));
+}
+template <bool BF>
+__device__ __forceinline__ v2h f2o2_of_f32_results(float a, float b)
+{
+    if constexpr (BF) return f2bf2_of_f32_results(a, b);
+    else return f2h2_of_f32_results(a, b);
 }
 
 // Two fp32 values that are NOT results of an fp32 FMA/add in this kernel (e.g. MFMA accumulators) -> packed fp16 (RNE).
@@ -186,6 +257,16 @@ __device__ __forceinline__ int half_to_int8_bits(float q)
 __device__ __forceinline__ int quant_one(float x, float s)
 {
     return half_to_int8_bits(x / s);    // IEEE-correct fp32 division (hipcc default, no fast-math)
+}
+
+// One bf16 activation of a bf16 call: sat[-127, 127](rint(x / s)) with the IEEE fp32 quotient; a NaN quotient (0 / 0, inf / inf,
+// NaN elements) gives 0 (v_cvt_i32_f32).  Returned as the int8's low byte.
+__device__ __forceinline__ int quant_one_bf16(float x, float s)
+{
+    const float r = __builtin_rintf(x / s); // IEEE-correct fp32 division (no fast-math), v_rndne_f32
+    int i;
+    asm("v_cvt_i32_f32 %0, %1" : "=v"(i) : "v"(r)); // NaN -> 0, out of range saturates
+    return min(max(i, -127), 127) & 0xff;
 }
 
 // Same result as quant_one(x, s) given rs = fl32(1/s), without a division in the common case.

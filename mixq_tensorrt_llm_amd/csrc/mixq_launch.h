@@ -41,7 +41,13 @@ enum { EPI_DEQUANT = 0, EPI_DEQUANT_SILU = 1, EPI_INT32 = 2, EPI_DEQUANT_SILU_MU
                           // with v_mfma_f32_32x32x16_f16 (second pass of the two-pass fpA_intB GEMM, w8a16_gemm_kernels.hip)
        EPI_DEQUANT_BIAS = 5 }; // 5: EPI_DEQUANT, then D = fp16(D + bias[n]) on the rounded value (GemmParams::bias, the layer's fp16 [N]
                                // bias; the reference adds it after the plugin, plugin.py:158-160).  Kernel choice: the same as EPI_DEQUANT
+// 6 / 7: EPI_DEQUANT / EPI_DEQUANT_BIAS of a bf16 call (mixq_enqueue with inputDesc[0].type == MIXQ_TYPE_BF16): sA, fpA, fpW, the bias
+// and D are bf16; the outlier product runs on the bf16 MFMA and is rounded to bf16, D = bf16(fma(acc, sW sA, P)) (+ one bf16 add of
+// the bias).  sW stays fp16.  Kernel choice: the same as EPI_DEQUANT
+enum { EPI_DEQUANT_BF16 = 6, EPI_DEQUANT_BIAS_BF16 = 7 };
 constexpr bool epi_has_silu(int epi) { return epi == EPI_DEQUANT_SILU || epi == EPI_DEQUANT_SILU_MUL; }
+constexpr bool epi_bf16(int epi) { return epi == EPI_DEQUANT_BF16 || epi == EPI_DEQUANT_BIAS_BF16; }
+constexpr bool epi_bias(int epi) { return epi == EPI_DEQUANT_BIAS || epi == EPI_DEQUANT_BIAS_BF16; }
 
 // TP all-gather fused into the GEMM's store path (gemm_pp_kernels.hip, TP = true): every finished 32-row block of a wave
 // tile is written straight into this rank's column block of EVERY destination's [M, n_total] buffer (one-sided peer writes
@@ -91,7 +97,7 @@ struct GemmParams {
     void* splitk_ws;      // device scratch of gemm_splitk_workspace_size bytes whose arrival words are zero, or null: lets
                           // launch_gemm split K over 2 / 4 workgroups per 256x256 tile when the tiles alone cover at
                           // most half / a quarter of the CUs (gemm_pp_kernels.hip)
-    const uint16_t* bias; // fp16 [N] of EPI_DEQUANT_BIAS (added once, by whoever runs the final epilogue of an element), else null
+    const uint16_t* bias; // fp16 [N] of EPI_DEQUANT_BIAS (bf16 [N] of EPI_DEQUANT_BIAS_BF16) (added once, by whoever runs the final epilogue of an element), else null
 };
 
 hipError_t launch_gemm(const GemmParams& p, int epi, hipStream_t st);
@@ -140,6 +146,9 @@ bool w8a16_skinny_takes(int M, int N, int K); // the fpA_intB skinny form serves
 // the same form with the layer's fp16 [N] bias added to the rounded result (M <= 16, w8a16_skinny_takes only)
 hipError_t launch_w8a16_skinny_bias(const void* A, const uint8_t* Wq, const void* scale, void* Out, int M, int N, int K,
                                     const void* bias, hipStream_t st);
+// the same form for a bf16 call (bf16 A / Out / bias, fp16 scale; bias may be null)
+hipError_t launch_w8a16_skinny_bf16(const void* A, const uint8_t* Wq, const void* scale, void* Out, int M, int N, int K,
+                                    const void* bias, hipStream_t st);
 // fpA_intB measurement / test knobs (mixq_debug_set_gemm_variant 80..89, 831..834, 840..844, 850..858, 800 + ABL); `form`:
 //   -1 everything automatic | 0 narrow form | 1..4 wide form with 32 / 64 / 128 / 256-row tiles | 100 + ABL ablation of the
 //   256-row form | 200 / 201 / 202 two-pass form automatic / never / always, 203 / 204 its second pass on 256- / 128-row tiles
@@ -172,7 +181,8 @@ hipError_t launch_dequantization_silu(void* out, const int32_t* x, const void* s
 hipError_t launch_quant_extract(void* A, int8_t* qA, void* sA, void* fpA, const int32_t* ind, int M, int K, int O,
                                 bool zero, hipStream_t st,
                                 void* zero_words = nullptr, // (kSplitkWordsBytes to clear on the way, or null)
-                                int frag = 0); // qA layout: 0 row-major | 1 the skinny GEMM's fragment order (quant_frag_layout_supported)
+                                int frag = 0,  // qA layout: 0 row-major | 1 the skinny GEMM's fragment order (quant_frag_layout_supported)
+                                bool bf16 = false); // A, sA, fpA are bf16 (zero == false only): sA = bf16(amax / 127), q = sat(rint(x / sA))
 void set_quant_block_rows(int m); // measurement knob 1300 (rules) / 1301..1312 (64 << n rows)
 int quant_block_rows(int nvec, bool norm_producer); // rows up to which a whole 256-thread block takes one row of nvec 16-byte vectors
 bool quant_frag_layout_supported(int M, int K);   // the quantiser can write the fragment-major image for this shape
@@ -207,6 +217,9 @@ hipError_t launch_unpack_s4_columns(const uint8_t* weight, const int32_t* ind, i
                                     void* out, hipStream_t st);
 hipError_t launch_w8a16(const void* A, const uint8_t* Wq, const void* scale, void* Out, int M, int N, int K,
                         hipStream_t st, const void* bias = nullptr); // bias: fp16 [N] added to the rounded result, or null
+// the same GEMV for bf16 A / Out / bias (scale stays fp16): Out = bf16(sum_k fp32(A) (q - 128) * scale[n]), fp32 throughout
+hipError_t launch_w8a16_bf16(const void* A, const uint8_t* Wq, const void* scale, void* Out, int M, int N, int K,
+                             hipStream_t st, const void* bias);
 
 void note_gemm_kernel(const char* name);
 // TP all-gather of the output columns as one-sided peer writes + flags (tp_kernels.hip)

@@ -26,12 +26,17 @@ constexpr int QBLOCK = 256;
 // bytes 4 KiB apart (gemm_skinny_kernels.hip; 32 x 4096 x 4096: GEMM 7.9 -> 5.4 us).
 // (A K-slice-major image [K / 128][M][128 B] for the 256 x 256 ping-pong GEMM was FRAG == 2 for one build: GEMM -0.3 %, this kernel
 //  +7.6 %, end to end -0.35 %: removed; the GEMM keeps its reader, ablation 512.)
-template <int TPR, int MAXV, bool ZERO, int FRAG = 0>
+// BF (bf16 calls, ZERO == false only): A, sA and fpA are bf16; sA = bf16(fp32(amax) / 127), q = sat[-127, 127](rint(x / sA)) with the
+// IEEE fp32 quotient (a NaN quotient gives 0) -- the fp16 rule's fp16 rounding of the quotient would move integers near 127 by up to
+// 0.5 in bf16.
+template <int TPR, int MAXV, bool ZERO, int FRAG = 0, bool BF = false>
 __global__ __launch_bounds__(QBLOCK) void quant_extract_kernel(uint16_t* __restrict__ A, int8_t* __restrict__ qA,
                                                                uint16_t* __restrict__ sA, uint16_t* __restrict__ fpA,
                                                                const int32_t* __restrict__ ind, int M, int K, int O,
                                                                unsigned* __restrict__ zero_words, void* dbg)
 {
+    static_assert(!(BF && ZERO), "the bf16 producer is the T flavour (A untouched)");
+    constexpr int INF_BITS = BF ? 0x7f80 : 0x7c00; // |x| bit pattern of +inf: larger patterns are NaNs
     dbg_stamp(dbg, 0); // (measurement only: NULL in production) entry
     // (enqueue: the hand-over words of the GEMM's K split over workgroups are cleared here, one launch earlier, instead
     //  of by a memset node of their own -- the plugin workspace is shared with whatever else the engine runs)
@@ -111,7 +116,7 @@ __global__ __launch_bounds__(QBLOCK) void quant_extract_kernel(uint16_t* __restr
     };
     const int amax_all = row_max((int)max(m2 & 0xffffu, m2 >> 16));
     int amax = amax_all;
-    if (amax_all > 0x7c00) { // the row holds a NaN: redo the max with NaNs dropped the way __hmax drops them
+    if (amax_all > INF_BITS) { // the row holds a NaN: redo the max with NaNs dropped the way __hmax drops them
         amax = -1;           // (-1 = every element is NaN)
 #pragma unroll
         for (int v = 0; v < MAXV; ++v) {
@@ -120,8 +125,8 @@ __global__ __launch_bounds__(QBLOCK) void quant_extract_kernel(uint16_t* __restr
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 int lo = (int)(w[e] & 0x7fffu), hi = (int)((w[e] >> 16) & 0x7fffu);
-                lo = lo > 0x7c00 ? -1 : lo;
-                hi = hi > 0x7c00 ? -1 : hi;
+                lo = lo > INF_BITS ? -1 : lo;
+                hi = hi > INF_BITS ? -1 : hi;
                 amax = max(amax, max(lo, hi));
             }
         }
@@ -129,8 +134,8 @@ __global__ __launch_bounds__(QBLOCK) void quant_extract_kernel(uint16_t* __restr
     }
     dbg_stamp(dbg, 3); // row data arrived, amax reduced
     const uint16_t amax_bits = amax < 0 ? (uint16_t)0x7fffu : (uint16_t)amax;
-    const uint16_t s_bits = f2h_bits(h2f(amax_bits) / 127.0f); // __hdiv(max, 127.0)
-    const float s = h2f(s_bits);
+    const uint16_t s_bits = BF ? f2bf_bits(bf2f(amax_bits) / 127.0f) : f2h_bits(h2f(amax_bits) / 127.0f); // __hdiv(max, 127.0)
+    const float s = o2f<BF>(s_bits);
     const float rs = 1.0f / s; // IEEE; inf for a zero scale, 0 for an infinite one (same special cases as x / s)
     if (row_ok && t == 0) sA[row] = s_bits;
 
@@ -145,7 +150,25 @@ __global__ __launch_bounds__(QBLOCK) void quant_extract_kernel(uint16_t* __restr
         return reinterpret_cast<uint2*>(qA + (blk << 10) + (((idx >> 1) & 3) << 8) + ((r & 15) << 4) + ((idx & 1) << 3));
     };
     const bool stream_out = FRAG == 0 && (int64_t)M * K >= ((int64_t)8 << 20); // (launch-uniform)
-    if (amax_all < 0x7c00 && s_bits != 0) { // every element finite, scale finite and non-zero (row-uniform)
+    if constexpr (BF) { // one IEEE quotient per element, every case (the row streams from HBM: the division hides under it)
+#pragma unroll
+        for (int v = 0; v < MAXV; ++v) {
+            const int idx = v * TPR + t;
+            if (row_ok && idx < nvec) {
+                typedef unsigned v2u_ __attribute__((ext_vector_type(2)));
+                const unsigned w[4] = {x[v].x, x[v].y, x[v].z, x[v].w};
+                unsigned o[2] = {0u, 0u};
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const int q0 = quant_one_bf16(bf2f((uint16_t)(w[e] & 0xffffu)), s);
+                    const int q1 = quant_one_bf16(bf2f((uint16_t)(w[e] >> 16)), s);
+                    o[e >> 1] |= (unsigned)(q0 | (q1 << 8)) << ((e & 1) * 16);
+                }
+                if (stream_out) __builtin_nontemporal_store(v2u_{o[0], o[1]}, reinterpret_cast<v2u_*>(slot(idx)));
+                else *slot(idx) = make_uint2(o[0], o[1]);
+            }
+        }
+    } else if (amax_all < 0x7c00 && s_bits != 0) { // every element finite, scale finite and non-zero (row-uniform)
 #pragma unroll
         for (int v = 0; v < MAXV; ++v) {
             const int idx = v * TPR + t;
@@ -194,13 +217,14 @@ __global__ __launch_bounds__(QBLOCK) void quant_extract_kernel(uint16_t* __restr
 }
 
 // Generic fallback for rows longer than 256 threads x 16 vectors (K > 32768): two passes over global memory.
-template <bool ZERO>
+template <bool ZERO, bool BF = false>
 __global__ __launch_bounds__(QBLOCK) void quant_extract_long_kernel(uint16_t* __restrict__ A, int8_t* __restrict__ qA,
                                                                     uint16_t* __restrict__ sA,
                                                                     uint16_t* __restrict__ fpA,
                                                                     const int32_t* __restrict__ ind, int M, int K, int O,
                                                                     unsigned* __restrict__ zero_words)
 {
+    constexpr int INF_BITS = BF ? 0x7f80 : 0x7c00;
     if (zero_words != nullptr && blockIdx.x == 0)
         for (int i = threadIdx.x; i < (int)(kSplitkWordsBytes / 4); i += QBLOCK) zero_words[i] = 0u;
     __shared__ int red[QBLOCK / 64];
@@ -222,7 +246,7 @@ __global__ __launch_bounds__(QBLOCK) void quant_extract_long_kernel(uint16_t* __
     int amax = -1;
     for (int k = tid; k < K; k += QBLOCK) {
         int b = (ZERO && ((reinterpret_cast<const unsigned*>(zmask)[k >> 5] >> (k & 31)) & 1u)) ? 0 : (a[k] & 0x7fff);
-        amax = max(amax, b > 0x7c00 ? -1 : b);
+        amax = max(amax, b > INF_BITS ? -1 : b);
     }
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) amax = max(amax, __shfl_xor(amax, off, 64));
@@ -230,12 +254,13 @@ __global__ __launch_bounds__(QBLOCK) void quant_extract_long_kernel(uint16_t* __
     __syncthreads();
     amax = max(max(red[0], red[1]), max(red[2], red[3]));
     const uint16_t amax_bits = amax < 0 ? (uint16_t)0x7fffu : (uint16_t)amax;
-    const uint16_t s_bits = f2h_bits(h2f(amax_bits) / 127.0f);
-    const float s = h2f(s_bits);
+    const uint16_t s_bits = BF ? f2bf_bits(bf2f(amax_bits) / 127.0f) : f2h_bits(h2f(amax_bits) / 127.0f);
+    const float s = o2f<BF>(s_bits);
     if (tid == 0) sA[row] = s_bits;
     for (int k = tid; k < K; k += QBLOCK) {
         bool z = ZERO && ((reinterpret_cast<const unsigned*>(zmask)[k >> 5] >> (k & 31)) & 1u);
-        qA[row * (int64_t)K + k] = (int8_t)quant_one(z ? 0.f : h2f(a[k]), s);
+        if constexpr (BF) qA[row * (int64_t)K + k] = (int8_t)quant_one_bf16(bf2f(a[k]), s);
+        else qA[row * (int64_t)K + k] = (int8_t)quant_one(z ? 0.f : h2f(a[k]), s);
     }
     if (ZERO) {
         __syncthreads();
@@ -320,10 +345,42 @@ static void note_qe(bool nt)
     note_producer_kernel(n[nt ? 1 : 0].c_str());
 }
 
+// the bf16 producer's name: the fp16 form's name + " [bf16]"
+template <int TPR, int MAXV, int FRAG>
+static void note_qe_bf16(bool nt)
+{
+    static const std::string n[2] = {producer_form_name("quant_extract_kernel", TPR, MAXV, "ZERO", 0, FRAG, false) + " [bf16]",
+                                     producer_form_name("quant_extract_kernel", TPR, MAXV, "ZERO", 0, FRAG, true) + " [bf16]"};
+    note_producer_kernel(n[nt ? 1 : 0].c_str());
+}
+
+// bf16 calls: the same grid, the same forms, quant_extract_bf16_kernel
+template <int TPR, int MAXV>
+static hipError_t launch_qe_bf16(uint16_t* A, int8_t* qA, uint16_t* sA, uint16_t* fpA, const int32_t* ind, int M, int K, int O,
+                                 hipStream_t st, unsigned* zw, int frag)
+{
+    void* const dbg = g_quant_stamps.load(std::memory_order_relaxed);
+    if constexpr (TPR == 256 && MAXV <= 8) {
+        if (frag == 1) {
+            note_qe_bf16<TPR, MAXV, 1>(false);
+            hipLaunchKernelGGL((quant_extract_kernel<TPR, MAXV, false, 1, true>), dim3((unsigned)M), dim3(QBLOCK), 0, st, A, qA, sA, fpA, ind, M, K,
+                               O, zw, dbg);
+            return hipGetLastError();
+        }
+    }
+    if (frag != 0) return hipErrorInvalidValue;
+    constexpr int RPB = QBLOCK / TPR;
+    note_qe_bf16<TPR, MAXV, 0>((int64_t)M * K >= ((int64_t)8 << 20));
+    hipLaunchKernelGGL((quant_extract_kernel<TPR, MAXV, false, 0, true>), dim3((unsigned)((M + RPB - 1) / RPB)), dim3(QBLOCK), 0, st, A, qA, sA,
+                       fpA, ind, M, K, O, zw, dbg);
+    return hipGetLastError();
+}
+
 template <int TPR, int MAXV>
 static hipError_t launch_qe(uint16_t* A, int8_t* qA, uint16_t* sA, uint16_t* fpA, const int32_t* ind, int M, int K,
-                            int O, bool zero, hipStream_t st, unsigned* zw, int frag = 0)
+                            int O, bool zero, hipStream_t st, unsigned* zw, int frag = 0, bool bf16 = false)
 {
+    if (bf16) return launch_qe_bf16<TPR, MAXV>(A, qA, sA, fpA, ind, M, K, O, st, zw, frag);
     void* const dbg = g_quant_stamps.load(std::memory_order_relaxed);
     if constexpr (TPR == 256 && MAXV <= 8) {
         if (frag == 1) { // decode batches: qA in the skinny GEMM's fragment order (both flavours)
@@ -372,8 +429,9 @@ int quant_block_rows(int nvec, bool norm_producer)
 bool quant_frag_layout_supported(int M, int K) { return M > 0 && M <= 64 && K % 8 == 0 && K / 8 > 64 * 2 && K / 8 <= 256 * 8; }
 
 hipError_t launch_quant_extract(void* A, int8_t* qA, void* sA, void* fpA, const int32_t* ind, int M, int K, int O,
-                                bool zero, hipStream_t st, void* zero_words, int frag)
+                                bool zero, hipStream_t st, void* zero_words, int frag, bool bf16)
 {
+    if (bf16 && zero) return hipErrorInvalidValue; // (the bf16 producer is the T flavour)
     if (frag == 1 && !quant_frag_layout_supported(M, K)) return hipErrorInvalidValue;
     if (frag < 0 || frag > 1) return hipErrorInvalidValue;
     if (M <= 0) return hipSuccess;
@@ -385,17 +443,20 @@ hipError_t launch_quant_extract(void* A, int8_t* qA, void* sA, void* fpA, const 
     // Decode batches (few rows: the launch is a chain of latencies, not a stream): a whole 256-thread block per row, so
     // that a row is ONE load round trip of 1-4 vectors per lane instead of 8-16 on a single wavefront
     if ((M <= quant_block_rows(nvec, false) || frag == 1) && nvec > 64 * 2) {
-        if (nvec <= 256 * 2) return launch_qe<256, 2>(a, qA, s, f, ind, M, K, O, zero, st, zw, frag);
-        if (nvec <= 256 * 4) return launch_qe<256, 4>(a, qA, s, f, ind, M, K, O, zero, st, zw, frag);
+        if (nvec <= 256 * 2) return launch_qe<256, 2>(a, qA, s, f, ind, M, K, O, zero, st, zw, frag, bf16);
+        if (nvec <= 256 * 4) return launch_qe<256, 4>(a, qA, s, f, ind, M, K, O, zero, st, zw, frag, bf16);
     }
-    if (nvec <= 64 * 2) return launch_qe<64, 2>(a, qA, s, f, ind, M, K, O, zero, st, zw, frag);
-    if (nvec <= 64 * 4) return launch_qe<64, 4>(a, qA, s, f, ind, M, K, O, zero, st, zw, frag);
-    if (nvec <= 64 * 8) return launch_qe<64, 8>(a, qA, s, f, ind, M, K, O, zero, st, zw, frag);
-    if (nvec <= 64 * 16) return launch_qe<64, 16>(a, qA, s, f, ind, M, K, O, zero, st, zw, frag);
-    if (nvec <= 256 * 8) return launch_qe<256, 8>(a, qA, s, f, ind, M, K, O, zero, st, zw, frag);
-    if (nvec <= 256 * 16) return launch_qe<256, 16>(a, qA, s, f, ind, M, K, O, zero, st, zw, frag);
+    if (nvec <= 64 * 2) return launch_qe<64, 2>(a, qA, s, f, ind, M, K, O, zero, st, zw, frag, bf16);
+    if (nvec <= 64 * 4) return launch_qe<64, 4>(a, qA, s, f, ind, M, K, O, zero, st, zw, frag, bf16);
+    if (nvec <= 64 * 8) return launch_qe<64, 8>(a, qA, s, f, ind, M, K, O, zero, st, zw, frag, bf16);
+    if (nvec <= 64 * 16) return launch_qe<64, 16>(a, qA, s, f, ind, M, K, O, zero, st, zw, frag, bf16);
+    if (nvec <= 256 * 8) return launch_qe<256, 8>(a, qA, s, f, ind, M, K, O, zero, st, zw, frag, bf16);
+    if (nvec <= 256 * 16) return launch_qe<256, 16>(a, qA, s, f, ind, M, K, O, zero, st, zw, frag, bf16);
     dim3 grid((unsigned)M), block(QBLOCK);
-    if (zero) {
+    if (bf16) {
+        note_producer_kernel("quant_extract_long_kernel<ZERO=0> [bf16]");
+        hipLaunchKernelGGL((quant_extract_long_kernel<false, true>), grid, block, 0, st, a, qA, s, f, ind, M, K, O, zw);
+    } else if (zero) {
         note_producer_kernel("quant_extract_long_kernel<ZERO=1>");
         size_t sm = (size_t)((K + 31) / 32) * 4;
         hipLaunchKernelGGL((quant_extract_long_kernel<true>), grid, block, sm, st, a, qA, s, f, ind, M, K, O, zw);

@@ -832,6 +832,111 @@ __global__ __launch_bounds__(KW * 64) void w8a16_skinny_kernel(const uint16_t* _
     }
 }
 
+// bf16 twin of w8a16_skinny_kernel (bf16 calls of mixq_enqueue, M <= 4): q - 128 is exact in bf16, so the weight fragments go into
+// v_mfma_f32_16x16x32_bf16 unscaled with the bf16 token fragments, and the fp16 column scale multiplies the fp32 sum once before the
+// single bf16 rounding: Out = bf16(scale[n] * sum_k A[m,k] (q[k,n] - 128)) (+ one bf16 add of the bias).
+template <int MT, int KW, int CG, bool NTW, bool BIAS>
+__global__ __launch_bounds__(KW * 64) void w8a16_skinny_bf16_kernel(const uint16_t* __restrict__ A, const uint8_t* __restrict__ Wq,
+                                                                const uint16_t* __restrict__ scale,
+                                                                uint16_t* __restrict__ Out, int M, int N, int K,
+                                                                const uint16_t* __restrict__ bias)
+{
+    __shared__ v4f_ part[KW][CG][MT][64]; // [K part][column group][token tile][lane]
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int ln = lane & 15, kq = lane >> 4;
+    const int n0 = blockIdx.x * (16 * CG);
+
+    const int nblk = K >> 6; // 64-row blocks
+    const int per = (nblk + KW - 1) / KW;
+    const int b_begin = min(wave * per, nblk), b_end = min(b_begin + per, nblk);
+
+    const uint8_t* wsrc[CG];
+#pragma unroll
+    for (int cg = 0; cg < CG; ++cg) {
+        const int col = min(n0 + cg * 16 + ln, N - 1); // clamped columns are computed, never stored
+        wsrc[cg] = Wq + (int64_t)(col >> 1) * 2 * K + (col & 1) * 64 + kq * 16;
+    }
+    const uint16_t* asrc[MT];
+#pragma unroll
+    for (int t = 0; t < MT; ++t) asrc[t] = A + (int64_t)min(t * 16 + ln, M - 1) * K + kq * 16;
+
+    v4f_ acc[CG][MT];
+#pragma unroll
+    for (int cg = 0; cg < CG; ++cg)
+#pragma unroll
+        for (int t = 0; t < MT; ++t) acc[cg][t] = v4f_{0.f, 0.f, 0.f, 0.f};
+
+    constexpr int UB = CG == 1 ? 8 : CG == 2 ? 4 : 2; // blocks per batch: 8 weight loads + 2 UB MT token loads in flight per lane
+    for (int b0 = b_begin; b0 < b_end; b0 += UB) {
+        uint4 wv[UB][CG];
+        uint4 av[UB][MT][2];
+#pragma unroll
+        for (int u = 0; u < UB; ++u) {
+            const int b = min(b0 + u, b_end - 1); // (the tail re-reads the last block; its products are skipped below)
+#pragma unroll
+            for (int cg = 0; cg < CG; ++cg) wv[u][cg] = wload16<NTW>(wsrc[cg] + (int64_t)b * 128);
+#pragma unroll
+            for (int t = 0; t < MT; ++t) {
+                av[u][t][0] = *reinterpret_cast<const uint4*>(asrc[t] + b * 64);
+                av[u][t][1] = *reinterpret_cast<const uint4*>(asrc[t] + b * 64 + 8);
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < UB; ++u) {
+            if (b0 + u >= b_end) break;
+#pragma unroll
+            for (int cg = 0; cg < CG; ++cg) {
+                const unsigned d[4] = {wv[u][cg].x, wv[u][cg].y, wv[u][cg].z, wv[u][cg].w};
+                // q - 128 as exact bf16 pairs (even bytes: this MFMA's 8 k-values, odd bytes: the next one's)
+                const v4u ew = {wpair_bf16(d[0], 0, 2), wpair_bf16(d[1], 0, 2), wpair_bf16(d[2], 0, 2), wpair_bf16(d[3], 0, 2)};
+                const v4u ow = {wpair_bf16(d[0], 1, 3), wpair_bf16(d[1], 1, 3), wpair_bf16(d[2], 1, 3), wpair_bf16(d[3], 1, 3)};
+                const v8bf we = __builtin_bit_cast(v8bf, ew), wod = __builtin_bit_cast(v8bf, ow);
+#pragma unroll
+                for (int t = 0; t < MT; ++t) {
+                    acc[cg][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(we, __builtin_bit_cast(v8bf, av[u][t][0]), acc[cg][t], 0, 0, 0);
+                    acc[cg][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wod, __builtin_bit_cast(v8bf, av[u][t][1]), acc[cg][t], 0, 0, 0);
+                }
+            }
+        }
+    }
+
+#pragma unroll
+    for (int cg = 0; cg < CG; ++cg)
+#pragma unroll
+        for (int t = 0; t < MT; ++t) part[wave][cg][t][lane] = acc[cg][t];
+    __syncthreads();
+
+    // wave w finishes (column group, token tile) w: the KW parts are added in K order (a fixed order: same bits every run)
+    for (int job = wave; job < CG * MT; job += KW) {
+        const int cg = job / MT, t = job % MT;
+        v4f_ sum = part[0][cg][t][lane];
+#pragma unroll
+        for (int w2 = 1; w2 < KW; ++w2) sum += part[w2][cg][t][lane];
+        // C/D layout of the 16x16 MFMA: column (token) = lane % 16, rows (output columns) 4 * (lane / 16) + r
+        const int m = t * 16 + ln, n = n0 + cg * 16 + 4 * kq;
+        if (m >= M) continue;
+        uint16_t* dst = Out + (int64_t)m * N + n;
+        float sc[4]; // the fp16 column scales, applied once to the fp32 sums (columns n .. n + 3, clamped; past N never stored)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) sc[r] = h2f(scale[min(n + r, N - 1)]);
+        v2h lo = f2bf2_of_f32_results(sum[0] * sc[0], sum[1] * sc[1]), hi = f2bf2_of_f32_results(sum[2] * sc[2], sum[3] * sc[3]);
+        if constexpr (BIAS) { // the layer's bias: one bf16 add of the rounded result
+            unsigned bw[2];
+#pragma unroll
+            for (int r2 = 0; r2 < 2; ++r2)
+                bw[r2] = (unsigned)bias[min(n + 2 * r2, N - 1)] | ((unsigned)bias[min(n + 2 * r2 + 1, N - 1)] << 16);
+            lo = bf2_add(lo, bw[0]), hi = bf2_add(hi, bw[1]);
+        }
+        if (n + 3 < N && (N & 3) == 0) {
+            *reinterpret_cast<uint2*>(dst) = uint2{__builtin_bit_cast(unsigned, lo), __builtin_bit_cast(unsigned, hi)};
+        } else {
+            if (n + 1 < N) *reinterpret_cast<unsigned*>(dst) = __builtin_bit_cast(unsigned, lo);
+            if (n + 3 < N) *reinterpret_cast<unsigned*>(dst + 2) = __builtin_bit_cast(unsigned, hi);
+        }
+    }
+}
+
 // ---- the two-pass form (large M): dequantise W once, then the 256x256 ping-pong kernel with the fp16 MFMA -------------------
 // In the fused forms every weight is dequantised once per 64 / 128 token rows (3 packed-f16 VALU per 2 weights beside the
 // MFMAs: -25 % of the time of a full-chip launch when ablated).  From ~1300 tokens on it is cheaper to pay
@@ -1121,6 +1226,44 @@ static hipError_t launch_wo_skinny(const uint16_t* A, const uint8_t* Wq, const u
     }
     hipLaunchKernelGGL((w8a16_skinny_kernel<MT, KW, CG, false, BIAS>), grid, block, 0, st, A, Wq, scale, Out, M, N, K, bias);
     return hipGetLastError();
+}
+
+template <int MT, int KW, int CG, bool BIAS>
+static hipError_t launch_wo_skinny_bf16(const uint16_t* A, const uint8_t* Wq, const uint16_t* scale, uint16_t* Out, int M, int N,
+                                        int K, hipStream_t st, const uint16_t* bias)
+{
+    const dim3 grid((unsigned)((N + 16 * CG - 1) / (16 * CG))), block(KW * 64);
+    if (g_wo_nt.load() != 0 && (int64_t)N * K >= wo_nt_weight_bytes()) // (launch_wo_skinny's rule for MT == 1)
+        hipLaunchKernelGGL((w8a16_skinny_bf16_kernel<MT, KW, CG, true, BIAS>), grid, block, 0, st, A, Wq, scale, Out, M, N, K, bias);
+    else
+        hipLaunchKernelGGL((w8a16_skinny_bf16_kernel<MT, KW, CG, false, BIAS>), grid, block, 0, st, A, Wq, scale, Out, M, N, K, bias);
+    return hipGetLastError();
+}
+template <bool BIAS>
+static hipError_t launch_wo_skinny_bf16_pick(int pick, const uint16_t* a, const uint8_t* Wq, const uint16_t* s, uint16_t* o, int M,
+                                             int N, int K, hipStream_t st, const uint16_t* b)
+{
+    switch (pick) {
+    case 2: return launch_wo_skinny_bf16<1, 8, 2, BIAS>(a, Wq, s, o, M, N, K, st, b);
+    case 3: return launch_wo_skinny_bf16<1, 16, 2, BIAS>(a, Wq, s, o, M, N, K, st, b);
+    case 4: return launch_wo_skinny_bf16<1, 8, 4, BIAS>(a, Wq, s, o, M, N, K, st, b);
+    case 6: return launch_wo_skinny_bf16<1, 8, 1, BIAS>(a, Wq, s, o, M, N, K, st, b);
+    case 7: return launch_wo_skinny_bf16<1, 16, 1, BIAS>(a, Wq, s, o, M, N, K, st, b);
+    default: return launch_wo_skinny_bf16<1, 16, 4, BIAS>(a, Wq, s, o, M, N, K, st, b);
+    }
+}
+// M <= 4 rows of a bf16 call: the skinny form wherever w8a16_skinny_takes (the same pick as the fp16 call), bias or not
+hipError_t launch_w8a16_skinny_bf16(const void* A, const uint8_t* Wq, const void* scale, void* Out, int M, int N, int K,
+                                    const void* bias, hipStream_t st)
+{
+    const int pick = wo_skinny_pick(M, N, K);
+    if (pick == 0 || M > 16) return hipErrorInvalidValue;
+    const uint16_t* a = static_cast<const uint16_t*>(A);
+    const uint16_t* s = static_cast<const uint16_t*>(scale);
+    const uint16_t* b = static_cast<const uint16_t*>(bias);
+    uint16_t* o = static_cast<uint16_t*>(Out);
+    if (b != nullptr) return launch_wo_skinny_bf16_pick<true>(pick, a, Wq, s, o, M, N, K, st, b);
+    return launch_wo_skinny_bf16_pick<false>(pick, a, Wq, s, o, M, N, K, st, nullptr);
 }
 
 // M <= 4 rows with the layer's bias (mixq_enqueue_bias): the skinny form wherever w8a16_skinny_takes (same pick as without it)

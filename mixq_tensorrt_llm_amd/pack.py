@@ -55,15 +55,30 @@ def eetq_quant_weights(Wt: torch.Tensor):
 
 
 def pack_linear_weights(W: torch.Tensor, act_scales: torch.Tensor, num_outliers: int = NUM_OUTLIERS,
-                        outlier_weights: str = "fp16") -> dict:
+                        outlier_weights: str = "fp16", fp_dtype: torch.dtype = torch.float16) -> dict:
     """One layer of model_config_utils.py:421-466.  Returns numpy arrays keyed like the checkpoint tensors.
 
     outlier_weights = "fp16": the reference's T-flavour (fp_weight = original fp16 columns, :452).
     outlier_weights = "int8": the P-flavour / fpA_intB mode of BASELINE config 4 -- fp_weight = dequantised int8 columns
     ``q_weight[:, ind] * scale_col`` (MixQ/src/mixquant/modules/linear.py:204), so the outlier path carries exactly the
-    information the int8 weights have."""
-    assert W.dtype == torch.float16 and W.dim() == 2
+    information the int8 weights have.
+
+    fp_dtype = torch.bfloat16 (MI355X extension, a layer for bf16 calls of the operator): ``fp_weight = W[:, ind]`` in bf16 from the
+    caller's W (fp16 or bf16), returned as its uint16 bit patterns (numpy has no bf16).  Everything else is computed exactly as for
+    fp16, from W in fp16.  Only with outlier_weights = "fp16"."""
+    assert W.dim() == 2
     assert outlier_weights in ("fp16", "int8")
+    if fp_dtype not in (torch.float16, torch.bfloat16):
+        raise ValueError(f"fp_dtype must be torch.float16 or torch.bfloat16, not {fp_dtype}")
+    if fp_dtype == torch.bfloat16:
+        if outlier_weights != "fp16":
+            raise ValueError('outlier_weights="int8" has no bf16 form: its outlier columns are fp16 products by definition')
+        assert W.dtype in (torch.float16, torch.bfloat16)
+        fp_bf16 = W.cpu()[:, select_outlier_columns(act_scales, num_outliers).long()].to(torch.bfloat16)
+        out = pack_linear_weights(W.cpu().to(torch.float16), act_scales, num_outliers)
+        out["fp_weight"] = fp_bf16.contiguous().view(torch.int16).numpy().view(np.uint16)
+        return out
+    assert W.dtype == torch.float16
     W = W.cpu().clone()
     sW = weight_scales(W)                                     # :429-430
     qweight, eetq_scales, _ = eetq_quant_weights(W.t().contiguous())   # :437-441 (un-zeroed W^T)

@@ -31,6 +31,9 @@ def shard_packed(packed: Dict[str, np.ndarray], tp_size: int, rank: int) -> Dict
 
     ``qweight`` is sliced in the interleaved image: output-feature pair j owns bytes [j*2K, (j+1)*2K), so a
     contiguous range of pairs is a contiguous byte range (see csrc/decode_kernels.hip)."""
+    if np.asarray(packed["fp_weight"]).dtype == np.uint16:
+        raise ValueError("a bf16 MixQ layer (fp_weight in bf16) cannot be row-sharded: the tensor-parallel path (the fused all-gather, "
+                         "mixq_enqueue_tp) is fp16 only -- quantize with tp_size=1 or fp_dtype=torch.float16")
     N, K = packed["weight"].shape
     n0, n1 = shard_bounds(N, tp_size, rank)
     out = dict(packed)

@@ -119,22 +119,32 @@ class MixQPlugin:
         ``inputs`` are the 7 tensors of plugin.py:141-151, every one declared fp16 exactly as TensorRT sees them
         (int8 / int32 payloads travel as fp16 views).  ``bias`` (optional, [N]): cast to fp16 as the reference's
         ``cast(bias, x.dtype)`` (plugin.py:158-160) and added in the GEMM's epilogue (``mixq_enqueue_bias``): the same
-        bits as ``enqueue(inputs) + bias``, without the second pass over the output."""
+        bits as ``enqueue(inputs) + bias``, without the second pass over the output.
+
+        bf16 call (MI355X extension): a bf16 ``inputs[0]`` with a bf16 ``fp_weight`` (``inputs[3]``) and, if given, a bf16
+        ``bias``; the other inputs stay as above and the output is bf16.  Mixed fp16 / bf16 operands raise ``TypeError``."""
         assert len(inputs) == 7, "MixQ takes 7 inputs"
         A = inputs[0]
         if not A.is_cuda:
             raise _lib.MixQLibraryError("MixQ enqueue needs device tensors (no CPU path exists)")
-        for t in inputs:
-            assert t.dtype == torch.float16 and t.is_contiguous() and t.device == A.device
-        in_desc = (TensorDesc * 7)(*[TensorDesc.make(t.shape) for t in inputs])
+        bf16 = A.dtype == torch.bfloat16
+        act = torch.bfloat16 if bf16 else torch.float16
+        if inputs[3].dtype != act or (bf16 and bias is not None and bias.dtype != act):
+            raise TypeError(f"MixQ enqueue: A is {A.dtype} but fp_weight is {inputs[3].dtype}"
+                            + (f" and the bias {bias.dtype}" if bias is not None else "")
+                            + " (a bf16 call takes bf16 A, fp_weight and bias; an fp16 call fp16 A and fp_weight)")
+        for i, t in enumerate(inputs):
+            assert t.dtype == (act if i in (0, 3) else torch.float16) and t.is_contiguous() and t.device == A.device
+        in_desc = (TensorDesc * 7)(*[TensorDesc.make(t.shape, _lib.MIXQ_TYPE_BF16 if bf16 and i in (0, 3) else _lib.MIXQ_TYPE_HALF)
+                                     for i, t in enumerate(inputs)])
         out_desc = TensorDesc()
         _lib.check(self._lib.mixq_get_output_dimensions(self._h, 0, in_desc, 7, ctypes.byref(out_desc)),
                    "getOutputDimensions")
         out_shape = [out_desc.d[i] for i in range(out_desc.nbDims)]
         if output is None:
-            output = torch.empty(out_shape, dtype=torch.float16, device=A.device)
+            output = torch.empty(out_shape, dtype=act, device=A.device)
         else:
-            assert list(output.shape) == out_shape and output.dtype == torch.float16 and output.is_contiguous()
+            assert list(output.shape) == out_shape and output.dtype == act and output.is_contiguous()
         K = A.shape[-1]
         M = A.numel() // K if K else 0
         N = inputs[1].shape[0]
@@ -143,7 +153,7 @@ class MixQPlugin:
         in_ptrs = (ctypes.c_void_p * 7)(*[t.data_ptr() for t in inputs])
         out_ptrs = (ctypes.c_void_p * 1)(output.data_ptr())
         if bias is not None:
-            bias = fp16_bias(bias, N, A.device)
+            bias = fp16_bias(bias, N, A.device, act)
             with torch.cuda.device(A.device):
                 rc = self._lib.mixq_enqueue_bias(self._h, in_desc, ctypes.byref(out_desc), in_ptrs, out_ptrs,
                                                  ctypes.c_void_p(bias.data_ptr()), ctypes.c_void_p(workspace.data_ptr()),
@@ -157,10 +167,10 @@ class MixQPlugin:
         return output
 
 
-def fp16_bias(bias: torch.Tensor, n: int, device) -> torch.Tensor:
-    """The bias operand of the ``*_bias`` entries: fp16 [n] (``cast(bias, x.dtype)``, plugin.py:158-160), contiguous, on
-    ``device``, 16-byte aligned (a misaligned view is copied)."""
-    b = bias.to(device=device, dtype=torch.float16).contiguous().reshape(-1)
+def fp16_bias(bias: torch.Tensor, n: int, device, dtype=torch.float16) -> torch.Tensor:
+    """The bias operand of the ``*_bias`` entries: fp16 [n] (``cast(bias, x.dtype)``, plugin.py:158-160; ``dtype`` bf16 for a
+    bf16 call), contiguous, on ``device``, 16-byte aligned (a misaligned view is copied)."""
+    b = bias.to(device=device, dtype=dtype).contiguous().reshape(-1)
     assert b.numel() == n, f"bias of {b.numel()} elements vs {n} output features"
     return b if b.data_ptr() % 16 == 0 else b.clone()
 
@@ -176,6 +186,9 @@ class MixQLinear:
 
     ``weight`` fp16 [N, K/2] (= int8 [N,K]) | ``fp_weight`` fp16 [N,128] | ``fp_ind`` fp16 [256] (= int32 [128]) |
     ``qweight`` fp16 [K, N/2] (= uint8 [K,N], EETQ-interleaved) | ``weights_scaling_factor`` fp16 [N] | optional ``bias``.
+
+    ``dtype=torch.bfloat16`` (MI355X extension): ``fp_weight`` and ``bias`` are bf16, ``forward`` takes and returns bf16 (bf16
+    calls of the operator); load it with ``pack.pack_linear_weights(..., fp_dtype=torch.bfloat16)``.  The default stays fp16.
     """
 
     def __init__(self, in_features: int, out_features: int, bias: bool = False, dtype=None, tp_group=None,
@@ -185,8 +198,11 @@ class MixQLinear:
         self.tp_size, self.tp_group, self.gather_output = tp_size, tp_group, gather_output
         dev = torch.device(device)
         f16 = dict(dtype=torch.float16, device=dev)
+        self.dtype = torch.bfloat16 if dtype == torch.bfloat16 else torch.float16  # of A, fp_weight, the bias and the output
+        if self.dtype == torch.bfloat16 and tp_size > 1:
+            raise ValueError("a bf16 MixQLinear cannot be row-sharded (tp_size > 1): the tensor-parallel path is fp16 only")
         self.weight = torch.zeros(self.out_features, in_features // 2, **f16)
-        self.fp_weight = torch.zeros(self.out_features, NUM_OUTLIERS, **f16)
+        self.fp_weight = torch.zeros(self.out_features, NUM_OUTLIERS, dtype=self.dtype, device=dev)
         self.fp_ind = torch.zeros(NUM_OUTLIERS * 2, **f16)
         self.qweight = torch.zeros(in_features, self.out_features // 2, **f16)
         self.weights_scaling_factor = torch.zeros(self.out_features, **f16)
@@ -221,12 +237,16 @@ class MixQLinear:
         had_image = self.weight_image is not None
         self.prepare_decode_batches(False)               # (a registered copy belongs to the OLD weight tensor)
         self.weight = carrier(packed["weight"], (N, K // 2))
-        self.fp_weight = carrier(packed["fp_weight"], (N, NUM_OUTLIERS))
+        fpw = packed["fp_weight"]
+        if (fpw.dtype == np.uint16) != (self.dtype == torch.bfloat16):  # (numpy has no bf16: pack ships bf16 as its uint16 bits)
+            raise TypeError(f"fp_weight of dtype {fpw.dtype} for a {self.dtype} layer: pack with fp_dtype={self.dtype}")
+        self.fp_weight = carrier(fpw, (N, NUM_OUTLIERS)).view(self.dtype)
         self.fp_ind = carrier(packed["fp_ind"].astype(np.int32), (NUM_OUTLIERS * 2,))
         self.qweight = carrier(packed["qweight"], (K, N // 2))
         self.weights_scaling_factor = carrier(packed["weights_scaling_factor"], (N,))
         if self.bias is not None and packed.get("bias") is not None:
-            b = torch.from_numpy(np.ascontiguousarray(packed["bias"])).to(dev)
+            b = np.ascontiguousarray(packed["bias"])
+            b = (torch.from_numpy(b.view(np.int16)).view(torch.bfloat16) if b.dtype == np.uint16 else torch.from_numpy(b)).to(dev)
             assert tuple(b.shape) == (N,), f"bias {tuple(b.shape)} vs this rank's {N} output features"
             self.bias = b.to(self.bias.dtype)
         if had_image:

@@ -86,16 +86,18 @@ def rank_major_rows(parts: Sequence[int], tp_size: int) -> np.ndarray:
 
 def quantize_layer(state_dict: Mapping[str, torch.Tensor], act_scales: Mapping[str, torch.Tensor], layer: int, which: str, *,
                    tp_size: int = 1, fix_quirk4: bool = False, qkv_layout: str = "contiguous", outlier_weights: str = "fp16",
-                   prefix: str = "model.layers") -> Dict[str, np.ndarray]:
-    """The seven tensors (+ bias) of one MixQ linear, full N; ``qkv_layout``: see quantize_model."""
+                   prefix: str = "model.layers", fp_dtype: torch.dtype = torch.float16) -> Dict[str, np.ndarray]:
+    """The seven tensors (+ bias) of one MixQ linear, full N; ``qkv_layout``, ``fp_dtype``: see quantize_model."""
     W, bias, parts = hf_linear(state_dict, layer, which, prefix)
     if tp_size > 1 and qkv_layout == "per_rank_heads" and len(parts) > 1:
         order = torch.from_numpy(rank_major_rows(parts, tp_size))
         W = W[order]
         bias = bias[order] if bias is not None else None
     scales = act_scales[act_scale_key(layer, which, fix_quirk4)]
-    packed = pack.pack_linear_weights(W, torch.as_tensor(scales), outlier_weights=outlier_weights)
-    if bias is not None:
+    packed = pack.pack_linear_weights(W, torch.as_tensor(scales), outlier_weights=outlier_weights, fp_dtype=fp_dtype)
+    if bias is not None and fp_dtype == torch.bfloat16:   # (bf16 bit patterns, like fp_weight)
+        packed["bias"] = bias.cpu().to(torch.bfloat16).contiguous().view(torch.int16).numpy().view(np.uint16)
+    elif bias is not None:
         packed["bias"] = bias.cpu().numpy()
     return packed
 
@@ -103,7 +105,7 @@ def quantize_layer(state_dict: Mapping[str, torch.Tensor], act_scales: Mapping[s
 def quantize_model(state_dict: Mapping[str, torch.Tensor], act_scales: Union[str, Mapping[str, torch.Tensor]], num_layers: int, *,
                    tp_size: int = 1, out_dir: Optional[str] = None, fix_quirk4: bool = False, qkv_layout: str = "contiguous",
                    outlier_weights: str = "fp16", config: Optional[dict] = None, prefix: str = "model.layers",
-                   ) -> Dict[str, Dict[str, np.ndarray]]:
+                   fp_dtype: torch.dtype = torch.float16) -> Dict[str, Dict[str, np.ndarray]]:
     """Walk the decoder layers like pack_linear_weights (model_config_utils.py:405-466) and, with ``out_dir``, write
     ``config.json`` + ``rank{r}.safetensors`` (checkpoint.save_checkpoint: fp16 carriers under the MixQLinear parameter names).
 
@@ -115,6 +117,8 @@ def quantize_model(state_dict: Mapping[str, torch.Tensor], act_scales: Union[str
     qkv_layout   "contiguous": rank r owns rows [r N/tp, (r+1) N/tp) of q | k | v, the all-gather returns [q | k | v];
                  "per_rank_heads": rank r owns [q_r | k_r | v_r] -- the reference's own split (rank_major_rows), for a runtime
                  whose attention consumes the local shard without a gather.
+    fp_dtype     torch.bfloat16: layers for bf16 calls of the operator (fp_weight and bias in bf16, pack.pack_linear_weights);
+                 the default walk (fp16) is unchanged.
     Returns {module prefix: packed tensors in true dtypes, full N} (what save_checkpoint consumes)."""
     assert qkv_layout in ("contiguous", "per_rank_heads"), qkv_layout
     if isinstance(act_scales, str):
@@ -124,7 +128,7 @@ def quantize_model(state_dict: Mapping[str, torch.Tensor], act_scales: Union[str
         for which in checkpoint.LAYER_PREFIXES:   # [attention.qkv, mlp.gate, mlp.proj], the reference's order (:409-415)
             layers[checkpoint.layer_prefix(i, which)] = quantize_layer(
                 state_dict, act_scales, i, which, tp_size=tp_size, fix_quirk4=fix_quirk4, qkv_layout=qkv_layout,
-                outlier_weights=outlier_weights, prefix=prefix)
+                outlier_weights=outlier_weights, prefix=prefix, fp_dtype=fp_dtype)
     if out_dir is not None:
         cfg = dict(config or {})
         cfg.setdefault("num_hidden_layers", num_layers)
