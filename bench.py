@@ -9,12 +9,16 @@ records around the GEMM launch).  Inputs (activations, packed weights) are resid
 
   python bench.py --gpus N --steps K --warmup W           (N>1: launched by torch.distributed.run, one rank per GPU)
   python bench.py ... --dump-outputs DIR                  (also writes the last timed step's outputs, see dump_last_step_outputs)
+  python bench.py ... --full                              (also the informational measurements, after the headline one)
 
 Multi-GPU: the path partitions over tokens with no data-path collective (each rank owns a full copy of the 4.6 GB of
 packed weights and its own token stream) -> default "dp", weak scaling.  `--tp T` runs the north-star TP layout
 instead (rows of W sharded T-ways, one RCCL all-gather of each fp16 output), strong scaling.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` and `cpu_baseline` objects.
+Prints ONE JSON line on rank 0: the contract fields, with `roofline` and `quantizer` objects derived from the events of the
+timed steps.  A plain run does nothing else: set up, warm up, time the steps, dump if asked, print.  `--full` adds the
+measurements that take runs of their own -- `small_m` / `config0`, `decode_step`, `int4`, `chunk_sweep`, `configs`,
+`cpu_baseline` and, at N > 1, the tp = N leg -- each of which a `--no-*` option leaves out again; `--mid-m` adds `mid_m`.
 """
 import argparse
 import ctypes
@@ -655,7 +659,10 @@ def main():
                          "of all three shapes (48 / 43 / 16 tile columns) fill the 256 CUs in whole rounds")
     ap.add_argument("--tp", type=int, default=1,
                     help="rows-of-W sharding degree of the MAIN measurement (1 = pure DP, no collective).  Whatever this "
-                         "is, a run on N > 1 GPUs also reports the north-star layout (tp = N) in the `tp` object")
+                         "is, a --full run on N > 1 GPUs also reports the north-star layout (tp = N) in the `tp` object")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline measurement, also run the informational ones (small_m, config0, decode_step, int4, "
+                         "chunk_sweep, configs, cpu_baseline; the tp = N leg at N > 1); the --no-* options leave parts out")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-decode-step", action="store_true", help="skip the decode_step object (profiling runs: 3 graphs of 96 calls)")
     ap.add_argument("--no-small-m", action="store_true", help="skip the small_m object (counter passes: thousands of short launches)")
@@ -905,7 +912,7 @@ def main():
                 max(elapsed - gemm_ms / 1e3, 1e-9) / n_launch),
         }
         try:  # informational small-M points (HBM-bound end of the operator); never part of `value`
-            if not args.no_small_m:
+            if args.full and not args.no_small_m:
                 res["small_m"] = small_m_points(lib, TensorDesc, dev, gen, st_ptr)
         except Exception as e:  # noqa: BLE001
             res["small_m"] = {"error": repr(e)}
@@ -932,12 +939,12 @@ def main():
                     "cpu_reference_us": None}
         except Exception as e:  # noqa: BLE001
             res["config0"] = {"error": repr(e)}
-        if world == 1 and not args.no_decode_step:
+        if world == 1 and args.full and not args.no_decode_step:
             try:
                 res["decode_step"] = decode_step_points(lib, TensorDesc, model, dev, gen)
             except Exception as e:  # noqa: BLE001
                 res["decode_step"] = {"error": repr(e)}
-        if world == 1 and not args.no_decode_step:
+        if world == 1 and args.full and not args.no_decode_step:
             try:
                 res["int4"] = int4_points(lib, model, dev, gen, res.get("decode_step"))
             except Exception as e:  # noqa: BLE001
@@ -949,7 +956,7 @@ def main():
                 res["mid_m"] = mid_m_points(lib, TensorDesc, dev, gen, st_ptr)
             except Exception as e:  # noqa: BLE001
                 res["mid_m"] = {"error": repr(e)}
-        if world == 1 and not args.no_sweeps:
+        if world == 1 and args.full and not args.no_sweeps:
             # ---- chunk_sweep + configs (VERDICT r3 #1c): the same path off the whole-round sweet spot of the headline chunk, and
             # on the other two BASELINE models.  Each point: whole model, every linear its own weights, GEMM events inside the
             # timed region (roofline-style frac of the int8 peak); never part of `value`.
@@ -1009,7 +1016,7 @@ def main():
                 res["configs"] = cfgs
             except Exception as e:  # noqa: BLE001
                 res["configs"] = {"error": repr(e)}
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             try:
                 res["cpu_baseline"] = cpu_baseline()
                 if isinstance(res.get("config0"), dict) and "error" not in res["config0"]:
@@ -1019,13 +1026,14 @@ def main():
                                        "sample": f"failed: {e}"}
     # ---- the north-star layout as a first-class object: rows of W sharded over ALL N ranks (tp = N) + one all-gather of
     # every fp16 output, the whole model, timed between the same barrier + synchronize brackets.  At N = 1 it is the main
-    # measurement itself.  A watchdog emits the main result and exits if the collective never comes back.
+    # measurement itself; otherwise it is a leg of its own, run by --full.  A watchdog emits the main result and exits if the
+    # collective never comes back.
     tp_obj = None
     if world == 1 or tp == world:
         tp_obj = {"tp": tp, "world_size": world, "value": value, "unit": "tokens/s", "ms_per_step": ms_per_step,
                   "steps": args.steps, "scaling": "strong", "collective": None if world == 1 else "all_gather",
                   "note": "identical to the main measurement" + (" (no collective at tp = 1)" if world == 1 else "")}
-    elif not args.no_tp_leg:
+    elif args.full and not args.no_tp_leg:
         import threading
 
         partial = {}   # what the leg has measured so far (the watchdog emits it instead of nothing)
@@ -1148,7 +1156,8 @@ def main():
         res["tp_tokens_per_s"] = (tp_obj or {}).get("value")
         res["value_layout"] = (f"{dp} data-parallel replica(s)" + (f" x tp{tp}" if tp > 1 else "") +
                                " -- no data-path collective at tp = 1; `tp_tokens_per_s` = the row-sharded layout (tp = N, "
-                               "strong scaling: the same tokens, W sharded N ways, one all-gather per linear)")
+                               "strong scaling: the same tokens, W sharded N ways, one all-gather per linear; null where "
+                               "that leg did not run: --full runs it)")
     if rank == 0:
         emit(res)   # the line first: a teardown that hangs (a rank that died inside the tp = N leg) must not cost it
     if world > 1:

@@ -398,8 +398,8 @@ def test_capturable_gather_does_not_overwrite_a_slow_peers_buffer(tmp_path):
 
 @pytest.mark.parametrize("gpus", [2, 4])
 def test_bench_self_launches(tmp_path, gpus):
-    """`python bench.py --gpus N ...` exactly as the driver types it (no torch.distributed.run in front, no WORLD_SIZE):
-    bench.py spawns its own ranks; rank 0 prints the ONE JSON line; the north-star layout (tp = N) ran with a named
+    """`python bench.py --gpus N ... --full` exactly as the driver types it (no torch.distributed.run in front, no WORLD_SIZE):
+    bench.py spawns its own ranks; rank 0 prints the ONE JSON line; the north-star layout (tp = N, a --full leg) ran with a named
     transport and no error.  All ranks share the one GPU of the box (MIXQ_BENCH_SINGLE_GPU_RANKS=1: gloo for the
     harness collectives) -- control flow, not a measurement.  N = 4: its shard widths (3072 / 2752 / 1024 rows), four-way
     transport self-tests and the transport comparison execute here first; more ranks would put more than six processes on
@@ -411,7 +411,7 @@ def test_bench_self_launches(tmp_path, gpus):
         env.pop(k, None)
     tokens = "16384" if gpus == 2 else "8192"
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--tokens", tokens, "--steps", "1",
-                        "--warmup", "1", "--config5-layers", "1"], capture_output=True, text=True, env=env, timeout=1500)
+                        "--warmup", "1", "--full", "--config5-layers", "1"], capture_output=True, text=True, env=env, timeout=1500)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, r.stdout[-2000:]

@@ -14,9 +14,9 @@ echo "== smoke"
 timeout 300 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -5 | tee "$OUT/smoke.log"
 echo "== bench"
 if [ "$MODE" = "full" ]; then
-  timeout 1200 python bench.py 2>&1 | tail -3 | tee "$OUT/bench.log"
+  timeout 1200 python bench.py --full 2>&1 | tail -3 | tee "$OUT/bench.log"
 else
-  timeout 600 python bench.py --tokens 131072 --steps 1 --warmup 1 2>&1 | tail -3 | tee "$OUT/bench.log"
+  timeout 600 python bench.py --tokens 131072 --steps 1 --warmup 1 --full 2>&1 | tail -3 | tee "$OUT/bench.log"
 fi
 echo "== mid-M leg (short prefill, K split over workgroups)"
 timeout 600 python bench.py --tokens 65536 --steps 1 --warmup 1 --no-cpu-baseline --mid-m 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(json.dumps(d['mid_m']))" | tee "$OUT/mid_m.json"

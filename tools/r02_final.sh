@@ -3,7 +3,7 @@
 set -u
 OUT=gpurun_out/r02_final; mkdir -p $OUT
 export TMPDIR=/tmp
-echo "== bench.py (defaults: 30 steps, 10 warm-up)"; timeout 1500 python bench.py 2>$OUT/bench.err | tail -1 | tee $OUT/bench_full.json | cut -c1-600
+echo "== bench.py --full (30 steps, 10 warm-up)"; timeout 1500 python bench.py --full 2>$OUT/bench.err | tail -1 | tee $OUT/bench_full.json | cut -c1-600
 echo "== mid-M leg"; timeout 600 python bench.py --tokens 65536 --steps 1 --warmup 1 --no-cpu-baseline --mid-m 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(json.dumps(d['mid_m']))" | tee $OUT/mid_m.json | cut -c1-400
 echo "== rocprofv3 kernel trace + stats"
 rm -rf "$OUT/prof"; mkdir -p "$OUT/prof"

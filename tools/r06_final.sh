@@ -11,7 +11,7 @@ python tools/pmc_traffic_update.py --note "${PMC_NOTE:-tools/r06_final.sh}" && c
 rm -rf gpurun_out/pmc_bench/FETCH_SIZE gpurun_out/pmc_bench/WRITE_SIZE
 echo "== pytest -m gpu"; timeout 2400 python -m pytest tests -m gpu -q --timeout 1500 --durations=8 2>&1 | tail -18 | tee $OUT/pytest_gpu.log
 echo "== smoke"; timeout 300 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | grep -v amdgpu.ids | tail -4
-echo "== bench.py (defaults)"; T0=$SECONDS; timeout 1500 python bench.py 2>$OUT/bench.err | tail -1 | tee $OUT/bench_full.json | cut -c1-500; echo "bench wall $((SECONDS - T0)) s"
+echo "== bench.py --full"; T0=$SECONDS; timeout 1500 python bench.py --full 2>$OUT/bench.err | tail -1 | tee $OUT/bench_full.json | cut -c1-500; echo "bench wall $((SECONDS - T0)) s"
 echo "== rocprofv3 kernel trace + stats"
 rm -rf "$OUT/prof"; mkdir -p "$OUT/prof"
 ( cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d "$OLDPWD/$OUT/prof" -o mixq -- \
