@@ -29,7 +29,7 @@ enum {
     MIXQ_OK = 0,
     MIXQ_E_BADARG = 1,    /* null pointer, negative size, nbDims out of range */
     MIXQ_E_SHAPE = 2,     /* K/N not a multiple of 16 (the reference's CUTLASS 16-B alignment), O > 256 ... */
-    MIXQ_E_ALIGN = 3,     /* a device pointer is not 16-byte aligned */
+    MIXQ_E_ALIGN = 3,     /* a device pointer is not 16-byte aligned (or not aligned as its entry states) */
     MIXQ_E_HIP = 4,       /* a HIP launch failed; hipGetLastError() has the detail */
     MIXQ_E_WORKSPACE = 5, /* workspace pointer is null where one is needed */
     MIXQ_E_STALE = 6,     /* mixq_weight_image_verify: the bytes behind a registered weight pointer are not the registered weight's */
@@ -180,6 +180,8 @@ MIXQ_API int mixq_rmsnorm_extract_quant(int M, int K, const void* x_f16, const v
                                         void* stream);
 /* int8FusedDequantizeCUDA (kernel/i8gemm.cu:151-194): D = fp16(float(A.B^T) * (scale_col[n]*scale_row[m]) + y).
  * A int8 [M,K], B int8 [N,K], scale_row fp16 [M], scale_col fp16 [N], y/D fp16 [M,N] (y may alias D, may be NULL = 0).
+ * A, B, scale_col, y and D 16-byte aligned (MIXQ_E_ALIGN otherwise); scale_row is read element by element and needs no more than
+ * its fp16 alignment.  Every buffer is used at exactly its declared size (tests/test_gpu_buffer_contract.py).
  * `workspace` (the reference hands CUTLASS its scratch here): NULL, or device scratch for the K split over workgroups --
  * at least mixq_gemm_scratch_size(M,N,K) bytes, ZERO-FILLED before its first use, one per stream (see
  * mixq_gemm_mixed_scratch below).  NULL always selects the one-workgroup-per-tile kernels. */
@@ -309,13 +311,18 @@ MIXQ_API int mixq_dequantization_silu(void* out_f16, const int32_t* x, const voi
  * weight = EETQ-interleaved uint8 [K,N] consumed as stored, scale fp16 [N], Out fp16 [m,n].
  * m <= 4: the batched GEMV (weightOnlyBatchedGemv, :53-58); m > 4: the fpA_intB tensor-core GEMM (ft::gemm_fp16_int,
  * :59-69 -> fpA_intB_gemm_template.h:441-552) -- here fp16 MFMA with the int8 weights dequantised in registers
- * (csrc/w8a16_gemm_kernels.hip).  k % 64 == 0, n % 2 == 0.  The reference passes its GEMM no workspace (nullptr, 0). */
+ * (csrc/w8a16_gemm_kernels.hip).  k % 64 == 0, n % 2 == 0.  The reference passes its GEMM no workspace (nullptr, 0).
+ * Alignment: input and weight 16 bytes; scale is read element by element (fp16 alignment); output: the GEMV route (m <= 4 where the
+ * skinny form does not take the shape) stores element by element, every other form four fp16 of a row at once -- 8-byte aligned
+ * where n % 4 == 0, 4-byte aligned where n % 4 == 2 (rows then start 4 bytes off every other row, and pairs are stored).
+ * MIXQ_E_ALIGN otherwise, before anything is launched. */
 MIXQ_API int mixq_w8a16_gemm_forward(const void* input_f16, const uint8_t* weight, const void* scale_f16,
                                      void* output_f16, int m, int n, int k, void* stream);
 /* The same with caller-owned scratch (MI355X extension; CUTLASS' split-k workspace, fpA_intB_gemm_wrapper.cu:16-25, is the
  * counterpart): with few column tiles K is split over several workgroups per tile, which keeps every CU streaming
  * weights; large problems (from ~1300 tokens) run in two passes -- W dequantised once to fp16 in the scratch (n k 2 bytes
- * behind the hand-over words), then the fp16 ping-pong GEMM -- when the scratch is large enough, the fused form otherwise.
+ * behind the hand-over words), then the fp16 ping-pong GEMM -- when the scratch is large enough and the output is 16-byte aligned
+ * (the second pass stores 16-byte pieces of a row), the fused form otherwise.
  * mixq_w8a16_gemm_workspace_size(m,n,k) bytes (0: nothing to gain for this shape), ZERO-FILLED before its first use,
  * one per stream; it may be the same buffer as mixq_gemm_mixed_scratch's (every kernel leaves the hand-over words zero).
  * Results do not depend on whether / how K was split in the last bit only up to fp32 summation order: the parts are
@@ -327,7 +334,8 @@ MIXQ_API int mixq_w8a16_gemm_forward_ws(const void* input_f16, const uint8_t* we
 
 /* MLP fusion beyond the reference (MixQ/src/mixquant/modules/fused/mlp.py:57-64 runs int8FusedDequantizeSilu and then
  * `gate_output *= up_output` as a separate pass over [M,N]): D = fp16( fp16(silu(float(A.B^T)*(sc*sr) + y)) * mul ),
- * bit-identical to the two-step sequence, one pass.  mul = fp16 [M,N] (the up projection's output), 8-byte aligned. */
+ * bit-identical to the two-step sequence, one pass.  mul = fp16 [M,N] (the up projection's output), 16-byte aligned like y (the
+ * 256 x 256 and 128 x 256 tiles fetch it 16 bytes at a time): MIXQ_E_ALIGN otherwise, before anything is launched. */
 MIXQ_API int mixq_int8_fused_dequantize_silu_mul(const int8_t* A, const int8_t* B, const void* scale_row,
                                                  const void* scale_col, const void* y, const void* mul, void* D, int M,
                                                  int N, int K, char* workspace, void* stream);

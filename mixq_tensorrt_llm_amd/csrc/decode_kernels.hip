@@ -334,6 +334,7 @@ hipError_t launch_w8a16_bf16(const void* A, const uint8_t* Wq, const void* scale
                              const void* bias)
 {
     if (M <= 0 || N <= 0) return hipSuccess;
+    note_gemm_kernel("w8a16 GEMV (1..4 tokens)"); // reporting only
     if (bias != nullptr) return launch_w8a16_rows_bf16<true>(A, Wq, scale, Out, M, N, K, st, static_cast<const uint16_t*>(bias));
     return launch_w8a16_rows_bf16<false>(A, Wq, scale, Out, M, N, K, st, nullptr);
 }
@@ -342,6 +343,7 @@ hipError_t launch_w8a16(const void* A, const uint8_t* Wq, const void* scale, voi
                         hipStream_t st, const void* bias)
 {
     if (M <= 0 || N <= 0) return hipSuccess;
+    note_gemm_kernel("w8a16 GEMV (1..4 tokens)"); // reporting only
     if (bias != nullptr) return launch_w8a16_rows<true>(A, Wq, scale, Out, M, N, K, st, static_cast<const uint16_t*>(bias));
     return launch_w8a16_rows<false>(A, Wq, scale, Out, M, N, K, st, nullptr);
 }

@@ -45,6 +45,9 @@ constexpr size_t kWorkspaceAlign = 128; // kCudaMemAlign, TsinghuaMixQPlugin.cpp
 
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+// fpA_intB GEMM forms (w8a16_gemm_kernels.hip): four fp16 of a row leave as one 8-byte store where every row starts 8-byte aligned
+// (N % 4 == 0), as two 4-byte stores otherwise (N % 4 == 2)
+inline bool w8a16_out_aligned(const void* out, int N) { return (reinterpret_cast<uintptr_t>(out) & (N % 4 == 0 ? 7u : 3u)) == 0; }
 inline int hip_rc(hipError_t e) { return e == hipSuccess ? MIXQ_OK : MIXQ_E_HIP; }
 
 } // namespace
@@ -521,7 +524,8 @@ static int fused_dequant_impl(const int8_t* A, const int8_t* B, const void* scal
     p.sA = static_cast<const uint16_t*>(scale_row), p.sW = static_cast<const uint16_t*>(scale_col);
     p.Y = static_cast<const uint16_t*>(y), p.D = D;
     p.Mul = static_cast<const uint16_t*>(mul);
-    if (epi == mixq::EPI_DEQUANT_SILU_MUL && (!mul || (reinterpret_cast<uintptr_t>(mul) & 7u))) return MIXQ_E_BADARG;
+    if (epi == mixq::EPI_DEQUANT_SILU_MUL && !mul) return MIXQ_E_BADARG;
+    if (epi == mixq::EPI_DEQUANT_SILU_MUL && !aligned16(mul)) return MIXQ_E_ALIGN; // (the ping-pong kernels fetch it 16 bytes at a time)
     p.zeros = mixq::zero_page();
     p.M = M, p.N = N, p.K = K, p.O = 0;
     if (!p.zeros) return MIXQ_E_HIP;
@@ -956,7 +960,7 @@ int mixq_w8a16_gemm_forward_ws(const void* input, const uint8_t* weight, const v
     // fpA_intB_gemm_wrapper.cu:45-70: m <= SMALL_M_FAST_PATH -> the batched GEMV, else the mixed-input tensor-core GEMM
     if (m <= kSmallMFastPath && !mixq::w8a16_skinny_takes(m, n, k))
         return hip_rc(mixq::launch_w8a16(input, weight, scale, output, m, n, k, st));
-    if (k % 8 || (reinterpret_cast<uintptr_t>(output) & 3u)) return MIXQ_E_ALIGN;
+    if (k % 8 || !w8a16_out_aligned(output, n)) return MIXQ_E_ALIGN;
     const void* zeros = mixq::zero_page();
     if (!zeros) return MIXQ_E_HIP;
     if (workspace && !aligned16(workspace)) workspace = nullptr, workspace_bytes = 0;
@@ -1060,7 +1064,7 @@ static int enqueue_impl(const mixq_handle* h, const mixq_tensor_desc* inputDesc,
         hipStream_t st = static_cast<hipStream_t>(stream);
         if (!mixq::w8a16_skinny_takes((int)M, (int)N, (int)K))
             return hip_rc(mixq::launch_w8a16_bf16(A, q_weight, scaling_factors, Out, (int)M, (int)N, (int)K, st, bias));
-        if (K % 8 || (reinterpret_cast<uintptr_t>(Out) & 3u)) return MIXQ_E_ALIGN;
+        if (K % 8 || !w8a16_out_aligned(Out, (int)N)) return MIXQ_E_ALIGN;
         return hip_rc(mixq::launch_w8a16_skinny_bf16(A, q_weight, scaling_factors, Out, (int)M, (int)N, (int)K, bias, st));
     }
     if (!bias) return mixq_w8a16_gemm_forward(A, q_weight, scaling_factors, Out, (int)M, (int)N, (int)K, stream);
@@ -1070,7 +1074,7 @@ static int enqueue_impl(const mixq_handle* h, const mixq_tensor_desc* inputDesc,
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (!mixq::w8a16_skinny_takes((int)M, (int)N, (int)K))
         return hip_rc(mixq::launch_w8a16(A, q_weight, scaling_factors, Out, (int)M, (int)N, (int)K, st, bias));
-    if (K % 8 || (reinterpret_cast<uintptr_t>(Out) & 3u)) return MIXQ_E_ALIGN;
+    if (K % 8 || !w8a16_out_aligned(Out, (int)N)) return MIXQ_E_ALIGN;
     return hip_rc(mixq::launch_w8a16_skinny_bias(A, q_weight, scaling_factors, Out, (int)M, (int)N, (int)K, bias, st));
 }
 

@@ -248,10 +248,11 @@ __global__ __launch_bounds__(256 * WM) void w8a16_gemm_kernel(const uint16_t* __
             const int n = n0w + 8 * g + 4 * lh;
             uint16_t* dst = Out + (int64_t)m * N + n;
             const v2h lo = f2h2(acc[t][4 * g], acc[t][4 * g + 1]), hi = f2h2(acc[t][4 * g + 2], acc[t][4 * g + 3]);
-            if (n + 3 < N) {
+            if (n + 3 < N && (N & 3) == 0) { // (rows of N % 4 == 2 columns start 4 bytes off every other row: dword stores)
                 *reinterpret_cast<uint2*>(dst) = uint2{__builtin_bit_cast(unsigned, lo), __builtin_bit_cast(unsigned, hi)};
-            } else if (n < N) { // N % 4 == 2: the last quad is half valid
-                *reinterpret_cast<unsigned*>(dst) = __builtin_bit_cast(unsigned, lo);
+            } else {
+                if (n + 1 < N) *reinterpret_cast<unsigned*>(dst) = __builtin_bit_cast(unsigned, lo);
+                if (n + 3 < N) *reinterpret_cast<unsigned*>(dst + 2) = __builtin_bit_cast(unsigned, hi);
             }
         }
     }
@@ -694,10 +695,11 @@ __global__ __launch_bounds__(256 * (WMH == 3 ? 2 : WMH)) void w8a16_gemm_wide_ke
                 uint16_t* dst = Out + (int64_t)m * N + n;
                 const v2h lo = f2h2(acc[cb][t][4 * g], acc[cb][t][4 * g + 1]);
                 const v2h hi = f2h2(acc[cb][t][4 * g + 2], acc[cb][t][4 * g + 3]);
-                if (n + 3 < N) {
+                if (n + 3 < N && (N & 3) == 0) { // (rows of N % 4 == 2 columns start 4 bytes off every other row: dword stores)
                     *reinterpret_cast<uint2*>(dst) = uint2{__builtin_bit_cast(unsigned, lo), __builtin_bit_cast(unsigned, hi)};
-                } else if (n < N) { // N % 4 == 2: the last quad is half valid
-                    *reinterpret_cast<unsigned*>(dst) = __builtin_bit_cast(unsigned, lo);
+                } else {
+                    if (n + 1 < N) *reinterpret_cast<unsigned*>(dst) = __builtin_bit_cast(unsigned, lo);
+                    if (n + 3 < N) *reinterpret_cast<unsigned*>(dst + 2) = __builtin_bit_cast(unsigned, hi);
                 }
             }
         }
@@ -1258,6 +1260,7 @@ hipError_t launch_w8a16_skinny_bf16(const void* A, const uint8_t* Wq, const void
 {
     const int pick = wo_skinny_pick(M, N, K);
     if (pick == 0 || M > 16) return hipErrorInvalidValue;
+    note_gemm_kernel("w8a16 skinny (MFMA GEMV, K split inside the workgroup)");
     const uint16_t* a = static_cast<const uint16_t*>(A);
     const uint16_t* s = static_cast<const uint16_t*>(scale);
     const uint16_t* b = static_cast<const uint16_t*>(bias);
@@ -1272,6 +1275,7 @@ hipError_t launch_w8a16_skinny_bias(const void* A, const uint8_t* Wq, const void
 {
     const int pick = wo_skinny_pick(M, N, K);
     if (pick == 0 || M > 16 || bias == nullptr) return hipErrorInvalidValue;
+    note_gemm_kernel("w8a16 skinny (MFMA GEMV, K split inside the workgroup)");
     const uint16_t* a = static_cast<const uint16_t*>(A);
     const uint16_t* s = static_cast<const uint16_t*>(scale);
     const uint16_t* b = static_cast<const uint16_t*>(bias);
@@ -1304,6 +1308,18 @@ static hipError_t launch_wo_wide(const uint16_t* A, const uint8_t* Wq, const uin
     return hipGetLastError();
 }
 
+// Reporting only (mixq_debug_last_gemm_kernel): the form a call took -- "w8a16 wide cfg<1..6>[ registers][, K split over workgroups]"
+#define MIXQ_WO_WIDE_NAMES(c)                                                                          \
+    {{"w8a16 wide cfg" #c, "w8a16 wide cfg" #c ", K split over workgroups"},                             \
+     {"w8a16 wide cfg" #c " registers", "w8a16 wide cfg" #c " registers, K split over workgroups"}}
+static const char* wo_wide_name(int cfg, bool regs, bool split)
+{
+    static const char* const names[7][2][2] = {MIXQ_WO_WIDE_NAMES(0), MIXQ_WO_WIDE_NAMES(1), MIXQ_WO_WIDE_NAMES(2), MIXQ_WO_WIDE_NAMES(3),
+                                               MIXQ_WO_WIDE_NAMES(4), MIXQ_WO_WIDE_NAMES(5), MIXQ_WO_WIDE_NAMES(6)};
+    return names[cfg >= 0 && cfg < 7 ? cfg : 0][regs ? 1 : 0][split ? 1 : 0];
+}
+#undef MIXQ_WO_WIDE_NAMES
+
 hipError_t launch_w8a16_gemm(const void* A, const uint8_t* Wq, const void* scale, void* Out, int M, int N, int K,
                              void* scratch, size_t scratch_bytes, const void* zeros, hipStream_t st)
 {
@@ -1311,15 +1327,19 @@ hipError_t launch_w8a16_gemm(const void* A, const uint8_t* Wq, const void* scale
     const uint16_t* a = static_cast<const uint16_t*>(A);
     const uint16_t* s = static_cast<const uint16_t*>(scale);
     uint16_t* o = static_cast<uint16_t*>(Out);
-    if (wo_two_pass_wanted(M, N, K) && scratch != nullptr && scratch_bytes >= wo_two_pass_bytes(N, K)) {
+    // (the second pass stores whole 16-byte pieces of an output row: an output that is not 16-byte aligned keeps the fused forms)
+    if (wo_two_pass_wanted(M, N, K) && scratch != nullptr && scratch_bytes >= wo_two_pass_bytes(N, K) && (reinterpret_cast<uintptr_t>(Out) & 15u) == 0) {
         const int64_t groups = (int64_t)(N >> 1) * (K >> 3);
         uint16_t* const wf = reinterpret_cast<uint16_t*>(static_cast<char*>(scratch) + kSplitkWordsBytes);
         hipLaunchKernelGGL(w8a16_dequant_kernel, dim3((unsigned)((groups + 255) / 256)), dim3(256), 0, st, Wq, s, wf, N, K);
         if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+        note_gemm_kernel(wo_two_pass_tile(M, N, K) == 128 ? "w8a16 two-pass (dequantise once, fp16 ping-pong on 128-row tiles)"
+                                                          : "w8a16 two-pass (dequantise once, fp16 ping-pong on 256-row tiles)");
         if (wo_two_pass_tile(M, N, K) == 128) return launch_gemm_f16_pp128(A, wf, Out, M, N, K, zeros, st);
         return launch_gemm_f16_pp(A, wf, Out, M, N, K, zeros, st);
     }
     if (const int pick = wo_skinny_pick(M, N, K); pick != 0) {
+        note_gemm_kernel("w8a16 skinny (MFMA GEMV, K split inside the workgroup)");
         if (M <= 16) {
             switch (pick) {
             case 2: return launch_wo_skinny<1, 8, 2>(a, Wq, s, o, M, N, K, st);
@@ -1344,6 +1364,8 @@ hipError_t launch_w8a16_gemm(const void* A, const uint8_t* Wq, const void* scale
     const size_t need_wide = wo_wide_workspace(M, N, K); // 0: the plan with scratch is the narrow form or does not split K
     const WoWidePlan pl = wo_wide_plan(M, N, K, need_wide == 0 || (scratch != nullptr && scratch_bytes >= need_wide));
     if (pl.cfg != 0) {
+        note_gemm_kernel(wo_wide_name(pl.cfg, g_wo_rw.load() != 0 && g_wo_abl.load() == 0 && (pl.cfg == 1 || pl.cfg == 2 || pl.cfg == 5 || pl.cfg == 6),
+                                      pl.ks > 1));
         if (pl.cfg == 4) {
             switch (g_wo_abl.load()) { // measurement-only ablations of the 256-row form
             case 1: return launch_wo_wide<4, 2, 3, 1>(a, Wq, s, o, M, N, K, pl.ks, scratch, st);
@@ -1389,6 +1411,7 @@ hipError_t launch_w8a16_gemm(const void* A, const uint8_t* Wq, const void* scale
     // the narrow form addresses the weights with an absolute 32-bit per-lane offset (w8a16_gemm_kernel: wlane): a weight of 4 GiB
     // or more (a 256k-entry head on K = 16384) would wrap silently -- refuse it (the wide / skinny forms use 64-bit bases)
     if ((int64_t)N * (int64_t)K >= ((int64_t)1 << 32)) return hipErrorInvalidValue;
+    note_gemm_kernel("w8a16 narrow (256-token passes)");
     for (int m0 = 0; m0 < M; m0 += 256) { // 256-token passes (each streams the weights once)
         const int rows = M - m0 < 256 ? M - m0 : 256;
         const size_t need = wo_narrow_workspace(rows, N, K);

@@ -266,6 +266,18 @@ def test_argument_validation_returns_codes_and_never_touches_the_device():
     assert lib.mixq_gemm_mixed_scratch(None, p16, p16, p16, None, None, p16, 8, 64, 64, 0, p16, 64, None) == BADARG
     assert lib.mixq_int8_fused_dequantize(p16, p16, p16, p16, None, p16, 8, 64, 24, None, None) == SHAPE
     assert lib.mixq_int8_fused_dequantize_silu_mul(p16, p16, p16, p16, None, None, p16, 8, 64, 64, None, None) == BADARG
+    # pointers whose kernels need more than the element's alignment are refused before any launch (tests/test_gpu_buffer_contract.py
+    # runs every OTHER pointer at the minimum the entry accepts): SiluMul's multiplicand is fetched 16 bytes at a time by the ping-pong
+    # tiles; the fpA_intB GEMM forms store four fp16 of an output row at once where n % 4 == 0, pairs where n % 4 == 2
+    half8 = ctypes.c_void_p(p16.value + 8)
+    word4 = ctypes.c_void_p(p16.value + 4)
+    assert lib.mixq_int8_fused_dequantize_silu_mul(p16, p16, p16, p16, None, half8, p16, 8, 64, 64, None, None) == ALIGN
+    assert lib.mixq_int8_fused_dequantize_silu_mul(p16, p16, p16, p16, None, odd, p16, 8, 64, 64, None, None) == ALIGN
+    assert lib.mixq_int8_fused_dequantize_layout(p16, p16, p16, p16, None, half8, p16, 8, 64, 64, 3, 0, None, None) == ALIGN
+    assert lib.mixq_w8a16_gemm_forward_ws(p16, p16, odd, word4, 8, 64, 64, None, 0, None) == ALIGN      # n % 4 == 0: 8 bytes
+    assert lib.mixq_w8a16_gemm_forward_ws(p16, p16, odd, odd, 8, 66, 64, None, 0, None) == ALIGN        # n % 4 == 2: 4 bytes
+    assert lib.mixq_w8a16_gemm_forward(p16, p16, odd, word4, 8, 64, 64, None) == ALIGN
+    assert lib.mixq_w8a16_gemm_forward_ws(odd, p16, p16, p16, 8, 64, 64, None, 0, None) == ALIGN        # the activations: 16 bytes
     # 4-bit flavour and outlier helpers
     assert lib.mixq_int4quant(4, 60, p16, p16, p16, None) == SHAPE
     assert lib.mixq_int4_fused_dequantize(p16, p16, p16, p16, None, p16, 8, 64, 24, p16, None) == SHAPE
@@ -278,6 +290,26 @@ def test_argument_validation_returns_codes_and_never_touches_the_device():
     assert lib.mixq_find_outliers_workspace_size(4096) == 512 and lib.mixq_int4_fused_workspace_size(65, 64, 16) == 65 * 32 + 64 * 32 and lib.mixq_int4_fused_workspace_size(32, 64, 16) == 0 and lib.mixq_int4_fused_workspace_size(32, 0, 16) == 32 * 32
     for code in (1, 2, 3, 4, 5):
         assert lib.mixq_error_string(code)
+
+
+def test_guarded_buffers_place_and_check_their_guards():
+    """tests/guarded.py on CPU tensors: the body sits at the requested ``ptr % 256``, has exactly the declared size, the guard pattern
+    keeps its phase across the body, and a changed guard byte is reported with its offset."""
+    import guarded as G
+    g = G.Guarded(100, G.F16_NAN, init=np.arange(50, dtype=np.int16), guard=4096, offset=16, device="cpu")
+    assert g.ptr % 256 == 16 and g.body(np.int16).tolist() == list(range(50)) and g.guard_damage() is None
+    h = g.buf.numpy()
+    assert (h[g.start - 2], h[g.start - 1], h[g.end], h[g.end + 1]) == (0x00, 0x7E, 0x00, 0x7E) and g.end - g.start == 100
+    g.buf[g.end + 5] = 1
+    assert "back guard: 1 bytes changed, offsets 5 .. 5" in g.guard_damage()
+    g.set_guards(G.F16_ONE)
+    assert g.guard_damage() is None and g.get(np.int16)[1]
+    g.buf[g.start - 3] = 9
+    assert "front guard: 1 bytes changed, offsets -3 .. -3" in g.guard_damage() and not g.get(np.int16)[1]
+    for off in (0, 2, 4, 8):
+        g2 = G.Guarded(64, 0x5A, guard=256, offset=off, device="cpu")
+        assert g2.ptr % 256 == off and (g2.body(np.uint8) == 0x5A).all() and g2.guard_damage() is None
+    assert G.out_guard(16, 2) == 64 << 10 and G.out_guard(4608, 2) == 256 * 4608 * 2
 
 
 def test_scratch_of_any_shape_fits_the_plugin_workspace(lib):

@@ -17,6 +17,7 @@ import ctypes
 import numpy as np
 import pytest
 
+import guarded
 from conftest import make_layer
 
 torch = pytest.importorskip("torch")
@@ -92,29 +93,12 @@ def stream():
     return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
-class Guarded:
+class Guarded(guarded.Guarded):
     """A device buffer of ``nbytes`` with GUARD bytes of ``fill`` in front and behind (and, unless ``init`` is given, ``fill``
-    inside).  ``ptr`` is 256-byte aligned like the allocation."""
+    inside).  ``ptr`` is 256-byte aligned like the allocation.  (tests/guarded.py: the buffer every GPU test file shares.)"""
 
     def __init__(self, nbytes, fill, init=None):
-        self.n, self.fill = int(nbytes), fill
-        host = np.full(self.n + 2 * GUARD, fill, np.uint8)
-        if init is not None:
-            raw = np.ascontiguousarray(init).reshape(-1).view(np.uint8)
-            assert raw.size == self.n
-            host[GUARD:GUARD + self.n] = raw
-        self.buf = torch.from_numpy(host).to(dev())
-
-    @property
-    def ptr(self):
-        return self.buf.data_ptr() + GUARD
-
-    def get(self, dtype, shape=None):
-        """(body as ``dtype`` [shape], whether both guards are intact)."""
-        h = self.buf.cpu().numpy()
-        ok = bool((h[:GUARD] == self.fill).all() and (h[GUARD + self.n:] == self.fill).all())
-        body = h[GUARD:GUARD + self.n].copy().view(dtype)
-        return (body.reshape(shape) if shape is not None else body), ok
+        super().__init__(nbytes, fill, init, guard=GUARD, offset=0, device=dev())
 
 
 def take(lib, guarded, dtype, shape, what):
