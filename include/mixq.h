@@ -506,8 +506,9 @@ MIXQ_API int mixq_preprocess_weights_int8(uint8_t* preprocessed, const int8_t* r
 MIXQ_API int mixq_unprocess_weights_int8(int8_t* row_major, const uint8_t* preprocessed, size_t rows, size_t cols);
 
 /* ---- plan introspection (MI355X extension; host only, needs no GPU) ---------------------------------------------------------
- * What mixq_enqueue would launch for a call with M rows on an [N, K] layer (128 outlier columns, workspace sized by
- * mixq_workspace_size, knobs at their defaults), written as text into buf: the kernel family, its tile / split / weight route.  The
+ * The plan mixq_enqueue executes for a call with M rows on an [N, K] layer (128 outlier columns, workspace sized by
+ * mixq_workspace_size, knobs as they are set), written as text into buf: the kernel family, its tile / split / weight route -- printed from
+ * the same plan value the launch dispatches on, not from a second copy of the rules.  The
  * selection is a set of tables fitted on measurements; this entry makes them readable from the outside -- an integrator
  * can list the forms its model's shapes will take, and tests/golden/selection_table.json pins the answers on BASELINE.json's shapes so
  * that a rule change shows up as a diff of that table.  have_weight_image != 0: as if `weight` had a registered image.

@@ -504,6 +504,20 @@ int gemm_mid_tile_width(int M, int N, int xsplit)
     return fits96 ? 96 : 128;
 }
 
+// Rotated K walk (every tile row starts at its own slice, p.flags bit 2; integer sums commute: same bits): the tile rows of a column panel
+// then miss on DIFFERENT weight lines at any moment instead of all waiting for the same ones.  Taken where it measured ahead on three of
+// three boxes, cold: 4..7 tile rows, tiles not split along K (4608 x 3584 at 512 / 768 rows 24.2 / 24.5 -> 20.6 / 22.7, 22.1 / 25.0 -> 19.8 / 23.7,
+// 22.1 / 25.5 -> 20.8 / 24.6 us; 4096 x 4096 at 768 rows 26.0 -> 22.9, 26.0 -> 24.3, 26.3 -> 25.1; warm: level) -- profiles/r06_mid_final_sweep_cold.txt,
+// r06_mid_bn96_cold.txt, r06_mid_rot_rows_cold.txt.  Not with two tile rows (12288 / 11008 x 4096 at 256 rows: ahead on one box, behind on two, 8 %
+// behind warm), not at 8 rows (+2 %), and not with K split over workgroups: bimodal there (4096 x 11008 at 256 rows, four parts: 29.5 us in one
+// process, 35 in the next -- it tripped the selection gate).  Knobs 1411 / 1410 / 1412: never / every unsplit launch / always.
+bool gemm_mid_rotated_walk(int M, int xsplit)
+{
+    const int rotm = g_mid_rot.load();
+    const int tile_rows = (M + mid::BM - 1) / mid::BM;
+    return rotm == 2 || (rotm == 1 && xsplit <= 1) || (rotm == 3 && xsplit <= 1 && tile_rows >= 4 && tile_rows <= 7);
+}
+
 template <int EPI, int BN>
 static hipError_t launch_mid_cfg(const GemmParams& q, hipStream_t st)
 {
@@ -524,39 +538,22 @@ static hipError_t launch_mid_cfg(const GemmParams& q, hipStream_t st)
 }
 
 template <int EPI>
-static hipError_t launch_mid_epi(const GemmParams& p, hipStream_t st)
+static hipError_t launch_mid_epi(const GemmParams& p, const GemmPlan& pl, hipStream_t st)
 {
     GemmParams q = p;
     // one tile row: every weight line is read by exactly one workgroup -> non-temporal copies for weights of 32 MiB and more
     // (the rule of gemm_kernels.hip's launch_cfg)
     if (p.M <= mid::BM && (int64_t)p.N * p.K >= ((int64_t)32 << 20)) q.flags |= 2;
-    // Rotated K walk (every tile row starts at its own slice, p.flags bit 2; integer sums commute: same bits): the tile rows of a column panel
-    // then miss on DIFFERENT weight lines at any moment instead of all waiting for the same ones.  Taken where it measured ahead on three of
-    // three boxes, cold: 4..7 tile rows, tiles not split along K (4608 x 3584 at 512 / 768 rows 24.2 / 24.5 -> 20.6 / 22.7, 22.1 / 25.0 -> 19.8 / 23.7,
-    // 22.1 / 25.5 -> 20.8 / 24.6 us; 4096 x 4096 at 768 rows 26.0 -> 22.9, 26.0 -> 24.3, 26.3 -> 25.1; warm: level) -- profiles/r06_mid_final_sweep_cold.txt,
-    // r06_mid_bn96_cold.txt, r06_mid_rot_rows_cold.txt.  Not with two tile rows (12288 / 11008 x 4096 at 256 rows: ahead on one box, behind on two, 8 %
-    // behind warm), not at 8 rows (+2 %), and not with K split over workgroups: bimodal there (4096 x 11008 at 256 rows, four parts: 29.5 us in one
-    // process, 35 in the next -- it tripped the selection gate).  Knobs 1411 / 1410 / 1412: never / every unsplit launch / always.
-    const int rotm = g_mid_rot.load();
-    const int tile_rows = (p.M + mid::BM - 1) / mid::BM;
-    if (rotm == 2 || (rotm == 1 && p.xsplit <= 1) || (rotm == 3 && p.xsplit <= 1 && tile_rows >= 4 && tile_rows <= 7)) q.flags |= 4;
-    if (gemm_mid_tile_width(p.M, p.N, p.xsplit) == 96) return launch_mid_cfg<EPI, 96>(q, st);
+    if (pl.mid_rot) q.flags |= 4;
+    if (pl.mid_bn == 96) return launch_mid_cfg<EPI, 96>(q, st);
     return launch_mid_cfg<EPI, 128>(q, st);
 }
 
 // p.xsplit = workgroups per tile along K (1: the tiles alone); K % 128 == 0
-hipError_t launch_gemm_mid(const GemmParams& p, int epi, hipStream_t st)
+hipError_t launch_gemm_mid(const GemmParams& p, int epi, const GemmPlan& pl, hipStream_t st)
 {
     if (p.K % mid::KS != 0 || p.K <= 0) return hipErrorInvalidValue;
-    switch (epi) {
-    case EPI_DEQUANT: return launch_mid_epi<EPI_DEQUANT>(p, st);
-    case EPI_DEQUANT_SILU: return launch_mid_epi<EPI_DEQUANT_SILU>(p, st);
-    case EPI_DEQUANT_SILU_MUL: return launch_mid_epi<EPI_DEQUANT_SILU_MUL>(p, st);
-    case EPI_DEQUANT_BIAS: return launch_mid_epi<EPI_DEQUANT_BIAS>(p, st);
-    case EPI_DEQUANT_BF16: return launch_mid_epi<EPI_DEQUANT_BF16>(p, st);
-    case EPI_DEQUANT_BIAS_BF16: return launch_mid_epi<EPI_DEQUANT_BIAS_BF16>(p, st);
-    default: return launch_mid_epi<EPI_INT32>(p, st);
-    }
+    return with_epi<true>(epi, [&](auto e) { return launch_mid_epi<decltype(e)::value>(p, pl, st); });
 }
 
 } // namespace mixq

@@ -485,15 +485,11 @@ hipError_t launch_gemm_f16_pp128(const void* A, const void* B, void* D, int M, i
 
 hipError_t launch_gemm_pp128(const GemmParams& p, int epi, hipStream_t st)
 {
-    switch (epi) {
-    case EPI_DEQUANT: return launch_pp128_epi<EPI_DEQUANT>(p, st);
-    case EPI_DEQUANT_SILU: return launch_pp128_epi<EPI_DEQUANT_SILU>(p, st);
-    case EPI_DEQUANT_SILU_MUL: return launch_pp128_epi<EPI_DEQUANT_SILU_MUL>(p, st);
-    case EPI_DEQUANT_BIAS: return launch_pp128_epi<EPI_DEQUANT_BIAS>(p, st);
-    case EPI_DEQUANT_BF16: return launch_pp128_epi<EPI_DEQUANT_BF16>(p, st);
-    case EPI_DEQUANT_BIAS_BF16: return launch_pp128_epi<EPI_DEQUANT_BIAS_BF16>(p, st);
-    default: return launch_pp128_cfg<EPI_INT32, false, false>(p, st);
-    }
+    return with_epi<true>(epi, [&](auto e) {
+        constexpr int EPI = decltype(e)::value;
+        if constexpr (EPI == EPI_INT32) return launch_pp128_cfg<EPI_INT32, false, false>(p, st);
+        else return launch_pp128_epi<EPI>(p, st);
+    });
 }
 
 } // namespace mixq

@@ -1023,8 +1023,6 @@ SplitPlan gemm_splitk_plan(int M, int N, int K)
     return none;
 }
 
-int gemm_splitk_factor(int M, int N, int K) { return gemm_splitk_plan(M, N, K).s; }
-
 static size_t splitk_slot_bytes(int) // S shares of a 256x256 int32 tile's 1/S-th: the S - 1 foreign ones + the own share,
 {                                      // which is parked only when a workgroup defers (see the kernel header)
     return (size_t)pp::BM * pp::BN * 4;
@@ -1063,41 +1061,19 @@ static hipError_t launch_pp_splitk_epi(const GemmParams& p, hipStream_t st)
     return launch_pp_splitk_cfg<EPI, false, false, SPLITK>(p, st);
 }
 
-hipError_t launch_gemm_pp_splitk(const GemmParams& p_in, int epi, hipStream_t st)
+hipError_t launch_gemm_pp_splitk(const GemmParams& p_in, int epi, const GemmPlan& pl, hipStream_t st)
 {
-    const SplitPlan pl = gemm_splitk_plan(p_in.M, p_in.N, p_in.K);
-    const int s = pl.s;
+    const int s = pl.xs;
     if (s == 0 || p_in.splitk_ws == nullptr) return hipErrorInvalidValue;
     GemmParams p = p_in;
     p.splitk_solo = pl.solo;
     p.splitk_patience = g_splitk_patience.load();
-    switch (epi) {
-    case EPI_DEQUANT:
-        return s == 8   ? launch_pp_splitk_epi<EPI_DEQUANT, 8>(p, st)
-               : s == 4 ? launch_pp_splitk_epi<EPI_DEQUANT, 4>(p, st)
-                        : launch_pp_splitk_epi<EPI_DEQUANT, 2>(p, st);
-    case EPI_DEQUANT_SILU:
-        return s == 8   ? launch_pp_splitk_epi<EPI_DEQUANT_SILU, 8>(p, st)
-               : s == 4 ? launch_pp_splitk_epi<EPI_DEQUANT_SILU, 4>(p, st)
-                        : launch_pp_splitk_epi<EPI_DEQUANT_SILU, 2>(p, st);
-    case EPI_DEQUANT_SILU_MUL:
-        return s == 8   ? launch_pp_splitk_epi<EPI_DEQUANT_SILU_MUL, 8>(p, st)
-               : s == 4 ? launch_pp_splitk_epi<EPI_DEQUANT_SILU_MUL, 4>(p, st)
-                        : launch_pp_splitk_epi<EPI_DEQUANT_SILU_MUL, 2>(p, st);
-    case EPI_DEQUANT_BIAS:
-        return s == 8   ? launch_pp_splitk_epi<EPI_DEQUANT_BIAS, 8>(p, st)
-               : s == 4 ? launch_pp_splitk_epi<EPI_DEQUANT_BIAS, 4>(p, st)
-                        : launch_pp_splitk_epi<EPI_DEQUANT_BIAS, 2>(p, st);
-    case EPI_DEQUANT_BF16:
-        return s == 8   ? launch_pp_splitk_epi<EPI_DEQUANT_BF16, 8>(p, st)
-               : s == 4 ? launch_pp_splitk_epi<EPI_DEQUANT_BF16, 4>(p, st)
-                        : launch_pp_splitk_epi<EPI_DEQUANT_BF16, 2>(p, st);
-    case EPI_DEQUANT_BIAS_BF16:
-        return s == 8   ? launch_pp_splitk_epi<EPI_DEQUANT_BIAS_BF16, 8>(p, st)
-               : s == 4 ? launch_pp_splitk_epi<EPI_DEQUANT_BIAS_BF16, 4>(p, st)
-                        : launch_pp_splitk_epi<EPI_DEQUANT_BIAS_BF16, 2>(p, st);
-    default: return hipErrorInvalidValue;
-    }
+    return with_epi<false>(epi, [&](auto e) {
+        constexpr int EPI = decltype(e)::value;
+        return s == 8   ? launch_pp_splitk_epi<EPI, 8>(p, st)
+               : s == 4 ? launch_pp_splitk_epi<EPI, 4>(p, st)
+                        : launch_pp_splitk_epi<EPI, 2>(p, st);
+    });
 }
 
 hipError_t launch_gemm_pp_ablate(const GemmParams& p, int abl, hipStream_t st)
@@ -1123,15 +1099,11 @@ hipError_t launch_gemm_pp_ablate(const GemmParams& p, int abl, hipStream_t st)
 
 hipError_t launch_gemm_pp(const GemmParams& p, int epi, hipStream_t st)
 {
-    switch (epi) {
-    case EPI_DEQUANT: return launch_pp_epi<EPI_DEQUANT>(p, st);
-    case EPI_DEQUANT_SILU: return launch_pp_epi<EPI_DEQUANT_SILU>(p, st);
-    case EPI_DEQUANT_SILU_MUL: return launch_pp_epi<EPI_DEQUANT_SILU_MUL>(p, st);
-    case EPI_DEQUANT_BIAS: return launch_pp_epi<EPI_DEQUANT_BIAS>(p, st);
-    case EPI_DEQUANT_BF16: return launch_pp_epi<EPI_DEQUANT_BF16>(p, st);
-    case EPI_DEQUANT_BIAS_BF16: return launch_pp_epi<EPI_DEQUANT_BIAS_BF16>(p, st);
-    default: return launch_pp_cfg<EPI_INT32, false, false>(p, st);
-    }
+    return with_epi<true>(epi, [&](auto e) {
+        constexpr int EPI = decltype(e)::value;
+        if constexpr (EPI == EPI_INT32) return launch_pp_cfg<EPI_INT32, false, false>(p, st);
+        else return launch_pp_epi<EPI>(p, st);
+    });
 }
 
 } // namespace mixq

@@ -317,8 +317,6 @@ __global__ __launch_bounds__(KW * 64) void gemm_skinny_kernel(const GemmParams p
     }
 }
 
-static std::atomic<int> g_skinny_kw{0}; // measurement knob: force the K-split width (0 = auto)
-void set_skinny_kw(int kw) { g_skinny_kw.store(kw); }
 static std::atomic<int> g_skinny_nt{0}; // measurement knob: feature tiles per workgroup of the fragment-major form (0 = auto)
 void set_skinny_nt(int nt) { g_skinny_nt.store(nt); }
 // 16-column feature tiles per workgroup (fragment-major form).  Measured (tools/experimental/skinny_wide_probe.sh, 32 rows, us per
@@ -334,7 +332,7 @@ void set_skinny_wrows(int on) { g_skinny_wrows.store(on); }
 // weights once; the same rule as the registered images' and the W8A16 stream's): operator us cold, plain -> non-temporal: 12288 x 4096 at 8 / 32 rows
 // 15.9 / 19.3 -> 15.2 / 18.2, 4096 x 11008 17.5 / 19.6 -> 16.0 / 18.6, 8192 x 8192 19.5 / 20.9 -> 17.9 / 19.9; a loop over ONE such layer (warm: served by the
 // Infinity Cache) is 4-12 % slower by construction (profiles/r05_skinny_256B_runs_cold.txt).  Knob 886 / 887: always / never.
-static bool skinny_runs_nontemporal(int N, int K)
+bool skinny_runs_nontemporal(int N, int K)
 {
     const int m = g_skinny_wrows.load(std::memory_order_relaxed);
     return m == 2 || (m == 1 && (int64_t)N * K >= ((int64_t)32 << 20));
@@ -578,7 +576,7 @@ const void* resolve_weight_image(const void* weight, int N, int K, hipStream_t s
 
 void set_skinny_wfrag(int mode) { g_skinny_wfrag.store(mode); }
 
-// the weight route launch_skinny_kw takes (GemmParams::b_frag): 0 row-major in 64-byte pieces | 1 / 2 the registered image | 3 row-major in 256-byte runs
+// the weight route of the skinny launch (GemmParams::b_frag): 0 row-major in 64-byte pieces | 1 / 2 the registered image | 3 row-major in 256-byte runs
 int skinny_weight_route(int a_frag, bool image, int M, int N, int K)
 {
     const int mode = g_skinny_wfrag.load(std::memory_order_relaxed);
@@ -594,26 +592,23 @@ int skinny_weight_route(int a_frag, bool image, int M, int N, int K)
 }
 
 template <int EPI, int KW, int ABL = 0>
-static hipError_t launch_skinny_kw_impl(const GemmParams& p, hipStream_t st);
+static hipError_t launch_skinny_kw_impl(const GemmParams& p, const GemmPlan& pl, hipStream_t st);
 
 template <int EPI, int KW, int ABL = 0>
-static hipError_t launch_skinny_kw(const GemmParams& p_in, hipStream_t st)
+static hipError_t launch_skinny_kw(const GemmParams& p_in, const GemmPlan& pl, hipStream_t st)
 {
     GemmParams p = p_in;
-    p.b_frag = 0;
-    if (KW == 4 && ABL == 0 && EPI != EPI_INT32) {
-        p.b_frag = skinny_weight_route(p.a_frag, p.b_image != nullptr, p.M, p.N, p.K); // 1 / 2 image | 3 row-major, 256-byte runs | 0 pieces
-        if (p.b_frag == 1 || p.b_frag == 2) p.B = static_cast<const int8_t*>(p.b_image); // (resolved ONCE per call by the API layer)
-    }
-    return launch_skinny_kw_impl<EPI, KW, ABL>(p, st);
+    p.b_frag = pl.skinny_route; // 1 / 2 image | 3 row-major, 256-byte runs | 0 pieces (always 0 unless KW == 4, no ablation, not EPI_INT32)
+    if (p.b_frag == 1 || p.b_frag == 2) p.B = static_cast<const int8_t*>(p.b_image); // (resolved ONCE per call by the API layer)
+    return launch_skinny_kw_impl<EPI, KW, ABL>(p, pl, st);
 }
 
 template <int MT, int EPI, int KW, int NT>
-static hipError_t launch_skinny_frag(const GemmParams& p, dim3 grid, dim3 block, hipStream_t st)
+static hipError_t launch_skinny_frag(const GemmParams& p, bool nontemporal, dim3 grid, dim3 block, hipStream_t st)
 {
     if constexpr (KW == 4) {
         if (p.b_frag == 3) {
-            if (skinny_runs_nontemporal(p.N, p.K)) hipLaunchKernelGGL((gemm_skinny_kernel<MT, EPI, KW, 0, true, NT, 4>), grid, block, 0, st, p);
+            if (nontemporal) hipLaunchKernelGGL((gemm_skinny_kernel<MT, EPI, KW, 0, true, NT, 4>), grid, block, 0, st, p);
             else hipLaunchKernelGGL((gemm_skinny_kernel<MT, EPI, KW, 0, true, NT, 3>), grid, block, 0, st, p);
             return hipGetLastError();
         }
@@ -625,30 +620,30 @@ static hipError_t launch_skinny_frag(const GemmParams& p, dim3 grid, dim3 block,
 }
 
 template <int EPI, int KW, int ABL>
-static hipError_t launch_skinny_kw_impl(const GemmParams& p, hipStream_t st)
+static hipError_t launch_skinny_kw_impl(const GemmParams& p, const GemmPlan& pl, hipStream_t st)
 {
     const dim3 grid((unsigned)((p.N + 15) / 16)), block(KW * 64);
     const int mt = (p.M + 15) / 16;
     if constexpr (KW == 4 && ABL == 0 && EPI != EPI_INT32) {
         if (p.a_frag == 1) { // (decode batches: M <= 64)
             if (mt > 4) return hipErrorInvalidValue;
-            if (p.b_frag == 3 && mt >= 3 && skinny_feature_tiles(p.M, p.N, p.K, false) == 2) { // (256-byte runs: 32 features per workgroup)
+            if (mt >= 3 && pl.skinny_tiles == 2) { // (256-byte runs: 32 features per workgroup)
                 const dim3 grid2((unsigned)((p.N + 31) / 32));
-                return mt == 3 ? launch_skinny_frag<3, EPI, KW, 2>(p, grid2, block, st) : launch_skinny_frag<4, EPI, KW, 2>(p, grid2, block, st);
+                return mt == 3 ? launch_skinny_frag<3, EPI, KW, 2>(p, pl.skinny_nt, grid2, block, st) : launch_skinny_frag<4, EPI, KW, 2>(p, pl.skinny_nt, grid2, block, st);
             }
-            if (mt == 3) return launch_skinny_frag<3, EPI, KW, 1>(p, grid, block, st);
-            if (mt == 4) return launch_skinny_frag<4, EPI, KW, 1>(p, grid, block, st);
-            if (skinny_feature_tiles(p.M, p.N, p.K, p.b_frag == 1 || p.b_frag == 2) == 2) { // 32 features per workgroup
+            if (mt == 3) return launch_skinny_frag<3, EPI, KW, 1>(p, pl.skinny_nt, grid, block, st);
+            if (mt == 4) return launch_skinny_frag<4, EPI, KW, 1>(p, pl.skinny_nt, grid, block, st);
+            if (pl.skinny_tiles == 2) { // 32 features per workgroup
                 const dim3 grid2((unsigned)((p.N + 31) / 32));
-                return mt == 1 ? launch_skinny_frag<1, EPI, KW, 2>(p, grid2, block, st) : launch_skinny_frag<2, EPI, KW, 2>(p, grid2, block, st);
+                return mt == 1 ? launch_skinny_frag<1, EPI, KW, 2>(p, pl.skinny_nt, grid2, block, st) : launch_skinny_frag<2, EPI, KW, 2>(p, pl.skinny_nt, grid2, block, st);
             }
-            return mt == 1 ? launch_skinny_frag<1, EPI, KW, 1>(p, grid, block, st) : launch_skinny_frag<2, EPI, KW, 1>(p, grid, block, st);
+            return mt == 1 ? launch_skinny_frag<1, EPI, KW, 1>(p, pl.skinny_nt, grid, block, st) : launch_skinny_frag<2, EPI, KW, 1>(p, pl.skinny_nt, grid, block, st);
         }
     }
     if (p.a_frag != 0) return hipErrorInvalidValue;
     if constexpr (KW == 4 && ABL == 0 && EPI != EPI_INT32) {
         if (p.b_frag == 3) { // row-major qA, row-major weight in 256-byte runs
-            if (skinny_runs_nontemporal(p.N, p.K)) {
+            if (pl.skinny_nt) {
                 switch (mt) {
                 case 1: hipLaunchKernelGGL((gemm_skinny_kernel<1, EPI, KW, 0, false, 1, 4>), grid, block, 0, st, p); break;
                 case 2: hipLaunchKernelGGL((gemm_skinny_kernel<2, EPI, KW, 0, false, 1, 4>), grid, block, 0, st, p); break;
@@ -676,7 +671,7 @@ static hipError_t launch_skinny_kw_impl(const GemmParams& p, hipStream_t st)
 }
 
 template <int EPI>
-static hipError_t launch_skinny_epi(const GemmParams& p, hipStream_t st)
+static hipError_t launch_skinny_epi(const GemmParams& p, const GemmPlan& pl, hipStream_t st)
 {
     // KW = 4 everywhere: measured (tools/skinny_sweep.sh) 8 / 16 K-split waves are never faster, even for N = 4096
     // where KW = 4 leaves one wave per SIMD -- the kernel is bound by the qA re-reads through L1, not by occupancy.
@@ -686,38 +681,28 @@ static hipError_t launch_skinny_epi(const GemmParams& p, hipStream_t st)
     //  Rotating the K-step order per workgroup, so that the workgroups do not all ask for the same qA lines at the same moment:
     //  no change either -- 7.9-8.2 vs 8.3-8.7 us at M = 32 on 4096 x 4096 -- the L2 serves the broadcast.)
     if (p.a_frag == 1) { // fragment-major qA (decode batches): the one configuration that reads that image
-        if constexpr (EPI != EPI_INT32) return launch_skinny_kw<EPI, 4>(p, st);
+        if constexpr (EPI != EPI_INT32) return launch_skinny_kw<EPI, 4>(p, pl, st);
         return hipErrorInvalidValue;
     }
-    int kw = g_skinny_kw.load();
-    if (EPI == EPI_DEQUANT && kw >= 21 && kw <= 28) { // measurement-only ablations (variant 40 + 20 + ABL): wrong results
-        switch (kw - 20) {
-        case 1: return launch_skinny_kw<EPI, 4, 1>(p, st);
-        case 2: return launch_skinny_kw<EPI, 4, 2>(p, st);
-        case 3: return launch_skinny_kw<EPI, 4, 3>(p, st);
-        case 4: return launch_skinny_kw<EPI, 4, 4>(p, st);
-        default: return launch_skinny_kw<EPI, 4, 7>(p, st);
+    if (EPI == EPI_DEQUANT && pl.skinny_abl != 0) { // measurement-only ablations (variant 40 + 20 + ABL): wrong results
+        switch (pl.skinny_abl) {
+        case 1: return launch_skinny_kw<EPI, 4, 1>(p, pl, st);
+        case 2: return launch_skinny_kw<EPI, 4, 2>(p, pl, st);
+        case 3: return launch_skinny_kw<EPI, 4, 3>(p, pl, st);
+        case 4: return launch_skinny_kw<EPI, 4, 4>(p, pl, st);
+        default: return launch_skinny_kw<EPI, 4, 7>(p, pl, st);
         }
     }
-    if (kw == 0 || kw > 16) kw = 4;
-    if (kw >= 16) return launch_skinny_kw<EPI, 16>(p, st);
-    if (kw >= 8) return launch_skinny_kw<EPI, 8>(p, st);
-    return launch_skinny_kw<EPI, 4>(p, st);
+    if (pl.skinny_kw == 16) return launch_skinny_kw<EPI, 16>(p, pl, st);
+    if (pl.skinny_kw == 8) return launch_skinny_kw<EPI, 8>(p, pl, st);
+    return launch_skinny_kw<EPI, 4>(p, pl, st);
 }
 
 bool gemm_skinny_supported(const GemmParams& p) { return p.M <= 64 && p.O <= 256; }
 
-hipError_t launch_gemm_skinny(const GemmParams& p, int epi, hipStream_t st)
+hipError_t launch_gemm_skinny(const GemmParams& p, int epi, const GemmPlan& pl, hipStream_t st)
 {
-    switch (epi) {
-    case EPI_DEQUANT: return launch_skinny_epi<EPI_DEQUANT>(p, st);
-    case EPI_DEQUANT_SILU: return launch_skinny_epi<EPI_DEQUANT_SILU>(p, st);
-    case EPI_DEQUANT_SILU_MUL: return launch_skinny_epi<EPI_DEQUANT_SILU_MUL>(p, st);
-    case EPI_DEQUANT_BIAS: return launch_skinny_epi<EPI_DEQUANT_BIAS>(p, st);
-    case EPI_DEQUANT_BF16: return launch_skinny_epi<EPI_DEQUANT_BF16>(p, st);
-    case EPI_DEQUANT_BIAS_BF16: return launch_skinny_epi<EPI_DEQUANT_BIAS_BF16>(p, st);
-    default: return launch_skinny_epi<EPI_INT32>(p, st);
-    }
+    return with_epi<true>(epi, [&](auto e) { return launch_skinny_epi<decltype(e)::value>(p, pl, st); });
 }
 
 } // namespace mixq

@@ -344,18 +344,22 @@ static size_t qa_region_bytes(int64_t M, int64_t K)
     return b;
 }
 
-// Exchange scratch ONE mixq_enqueue call with exactly M rows carves behind fpA (the K splits over workgroups of
-// gemm_pp_kernels.hip / gemm_kernels.hip): the 256x256 form's from 129 rows on where its plan applies, else the small-tile form's.
-// enqueue_impl and the workspace bound below both go through this function, so they cannot disagree.
+// Exchange scratch of the K splits over workgroups (gemm_pp_kernels.hip / gemm_kernels.hip) for one GEMM with exactly M rows: the 256x256
+// form's from 129 rows on where its plan applies, else the small-tile form's.  NOT read off the call's plan on purpose:
+// (the mid-M deep form is chosen first where its table says so; the scratch also covers whichever form a forced schedule would
+//  fall back to on the same shape)
+static size_t gemm_scratch_bytes(int M, int N, int K)
+{
+    const size_t d = mixq::gemm_deep_workspace_size(M, N, K); // (0 unless the deep form splits K over workgroups)
+    size_t a = mixq::gemm_splitk_workspace_size(M, N, K);
+    if (!a) a = mixq::gemm_xsplit_workspace_size(M, N, K);
+    return d > a ? d : a;
+}
+// What ONE mixq_enqueue call with exactly M rows carves behind fpA: enqueue_impl and the workspace bound below both ask here
 static size_t enqueue_scratch_bytes(int64_t M, int64_t N, int64_t K)
 {
     if (M <= 4 || N <= 0 || K <= 0 || M > INT32_MAX || N > INT32_MAX || K > INT32_MAX) return 0;
-    // (the mid-M deep form is chosen first where its table says so; the scratch also covers whichever form a forced schedule would
-    //  fall back to on the same shape)
-    const size_t d = mixq::gemm_deep_takes((int)M, (int)N, (int)K, true) ? mixq::gemm_deep_workspace_size((int)M, (int)N, (int)K) : 0;
-    size_t a = M > 128 ? mixq::gemm_splitk_workspace_size((int)M, (int)N, (int)K) : 0;
-    if (!a) a = mixq::gemm_xsplit_workspace_size((int)M, (int)N, (int)K);
-    return d > a ? d : a;
+    return gemm_scratch_bytes((int)M, (int)N, (int)K);
 }
 // Largest exchange scratch mixq_enqueue can carve with these N, K and ANY M <= maxM.  The plans (gemm_splitk_plan, xsplit_plan,
 // deep_plan_auto) see M mostly through ceil(M / 32 | 64 | 128 | 256) and the thresholds 4 / 16 / 32 / 128 / 256, and are not monotone
@@ -509,6 +513,15 @@ int mixq_rmsnorm_extract_quant4(int M, int K, const void* x, const void* gamma, 
                                              M, K, len, 4, static_cast<hipStream_t>(stream)));
 }
 
+// The GemmParams a selection question is asked with: mixq::plan_gemm reads the shape, the qA layout and WHETHER there is scratch and an image
+static mixq::GemmParams plan_probe(int M, int N, int K, int O, int a_frag, const void* scratch, const void* image)
+{
+    mixq::GemmParams probe{};
+    probe.M = M, probe.N = N, probe.K = K, probe.O = O, probe.a_frag = a_frag;
+    probe.splitk_ws = const_cast<void*>(scratch), probe.b_image = image; // (a registered weight image widens the skinny kernel's range)
+    return probe;
+}
+
 static int fused_dequant_impl(const int8_t* A, const int8_t* B, const void* scale_row, const void* scale_col,
                               const void* y, void* D, int M, int N, int K, int epi, void* stream,
                               const void* mul = nullptr, void* scratch = nullptr, int a_frag = 0)
@@ -532,8 +545,9 @@ static int fused_dequant_impl(const int8_t* A, const int8_t* B, const void* scal
     if (scratch && aligned16(scratch)) p.splitk_ws = scratch; // K split over workgroups where the shape calls for it
     p.a_frag = a_frag;
     if (M <= 64) p.b_image = mixq::resolve_weight_image(B, N, K, static_cast<hipStream_t>(stream)); // (ONE lookup per call)
-    if (a_frag != 0 && !(a_frag == 1 && mixq::gemm_takes_skinny(p, epi))) return MIXQ_E_SHAPE; // (the image has ONE reader)
-    return hip_rc(mixq::launch_gemm(p, epi, static_cast<hipStream_t>(stream)));
+    const mixq::GemmPlan plan = mixq::plan_gemm(p, epi);
+    if (a_frag != 0 && !(a_frag == 1 && plan.family == mixq::GEMM_SKINNY)) return MIXQ_E_SHAPE; // (the image has ONE reader)
+    return hip_rc(mixq::launch_gemm(p, epi, static_cast<hipStream_t>(stream), &plan));
 }
 
 int mixq_int8_fused_dequantize(const int8_t* A, const int8_t* B, const void* scale_row, const void* scale_col,
@@ -681,15 +695,6 @@ int mixq_int8_fused_dequantize_silu_mul(const int8_t* A, const int8_t* B, const 
                               workspace);
 }
 
-// scratch of whichever cross-workgroup K split launch_gemm would pick for this shape (at most one applies)
-static size_t gemm_scratch_bytes(int M, int N, int K)
-{
-    const size_t d = mixq::gemm_deep_takes(M, N, K, true) ? mixq::gemm_deep_workspace_size(M, N, K) : 0;
-    size_t a = mixq::gemm_splitk_workspace_size(M, N, K);
-    if (!a) a = mixq::gemm_xsplit_workspace_size(M, N, K);
-    return d > a ? d : a;
-}
-
 size_t mixq_gemm_scratch_size(int M, int N, int K) { return gemm_scratch_bytes(M, N, K); }
 
 size_t mixq_gemm_scratch_bound(void)
@@ -707,7 +712,7 @@ int mixq_gemm_mixed(const int8_t* qA, const int8_t* W, const void* sA, const voi
 static int gemm_mixed_impl(const int8_t* qA, const int8_t* W, const void* sA, const void* sW, const void* fpA, const void* fpW,
                            void* Out, int M, int N, int K, int O, void* scratch, size_t scratch_bytes, void* stream,
                            int a_frag, const void* b_image = nullptr, bool image_resolved = false, const void* bias = nullptr,
-                           bool bf16 = false);
+                           bool bf16 = false, const mixq::GemmPlan* plan = nullptr);
 
 int mixq_gemm_mixed_scratch(const int8_t* qA, const int8_t* W, const void* sA, const void* sW, const void* fpA,
                             const void* fpW, void* Out, int M, int N, int K, int O, void* scratch, size_t scratch_bytes,
@@ -725,13 +730,20 @@ int mixq_gemm_mixed_bias(const int8_t* qA, const int8_t* W, const void* sA, cons
     return gemm_mixed_impl(qA, W, sA, sW, fpA, fpW, Out, M, N, K, O, scratch, scratch_bytes, stream, 0, nullptr, false, bias);
 }
 
+// the epilogue of a mixed GEMM with 128 outlier columns at most
+static int mixed_epi(bool bias, bool bf16)
+{
+    return bf16 ? (bias ? mixq::EPI_DEQUANT_BIAS_BF16 : mixq::EPI_DEQUANT_BF16) : (bias ? mixq::EPI_DEQUANT_BIAS : mixq::EPI_DEQUANT);
+}
+
 // a_frag: layout of qA (GemmParams::a_frag): enqueue's own quantiser may write the consuming kernel's preferred image; the
 // public entries take row-major qA
 // b_image / image_resolved: the caller has already looked the weight's image up for this call (one lookup per call)
 // bias: the layer's fp16 [N] bias (EPI_DEQUANT_BIAS: the same kernel as EPI_DEQUANT, one fp16 add in its epilogue), or null
+// plan: mixq_enqueue has planned this call already (O == kNumOutliers, scratch sized by gemm_scratch_bytes), or null
 static int gemm_mixed_impl(const int8_t* qA, const int8_t* W, const void* sA, const void* sW, const void* fpA, const void* fpW,
                            void* Out, int M, int N, int K, int O, void* scratch, size_t scratch_bytes, void* stream,
-                           int a_frag, const void* b_image, bool image_resolved, const void* bias, bool bf16)
+                           int a_frag, const void* b_image, bool image_resolved, const void* bias, bool bf16, const mixq::GemmPlan* plan)
 {
     if (M < 0 || N < 0 || K <= 0 || O < 0) return MIXQ_E_BADARG;
     if (M == 0 || N == 0) return MIXQ_OK;
@@ -750,14 +762,12 @@ static int gemm_mixed_impl(const int8_t* qA, const int8_t* W, const void* sA, co
     p.dbg = g_dbg_stamps.load(std::memory_order_relaxed);
     p.a_frag = a_frag;
     p.b_image = image_resolved ? b_image : (M <= 64 ? mixq::resolve_weight_image(W, N, K, st) : nullptr);
-    if (scratch && aligned16(scratch) && scratch_bytes >= gemm_scratch_bytes(M, N, K)) p.splitk_ws = scratch;
+    if (scratch && aligned16(scratch) && (plan || scratch_bytes >= gemm_scratch_bytes(M, N, K))) p.splitk_ws = scratch;
     if (O <= kNumOutliers) {
         p.fpA = static_cast<const uint16_t*>(fpA), p.fpW = static_cast<const uint16_t*>(fpW), p.O = O;
         p.bias = static_cast<const uint16_t*>(bias);
-        const int epi = bf16 ? (bias ? mixq::EPI_DEQUANT_BIAS_BF16 : mixq::EPI_DEQUANT_BF16)
-                             : (bias ? mixq::EPI_DEQUANT_BIAS : mixq::EPI_DEQUANT);
         g_last_gemm_bf16.store(bf16, std::memory_order_relaxed);
-        return hip_rc(mixq::launch_gemm(p, epi, st));
+        return hip_rc(mixq::launch_gemm(p, mixed_epi(bias != nullptr, bf16), st, plan));
     }
     if (bias || bf16) return MIXQ_E_SHAPE;
     // more outlier columns than one LDS pass holds: the reference's own two-step order (side GEMM into Out, then C = D = Out)
@@ -800,11 +810,8 @@ int mixq_qa_layout(int M, int N, int K)
 {
     if (M <= kSmallMFastPath || M > 64 || N <= 0 || K <= 0 || K % 16 || N % 16) return MIXQ_QA_ROW_MAJOR;
     if (!mixq::qa_frag_enabled() || !mixq::quant_frag_layout_supported(M, K)) return MIXQ_QA_ROW_MAJOR;
-    mixq::GemmParams probe{};
-    probe.M = M, probe.N = N, probe.K = K, probe.O = kNumOutliers, probe.a_frag = 1;
-    static int dummy;
-    if (gemm_scratch_bytes(M, N, K) != 0) probe.splitk_ws = &dummy; // (where a caller WITH scratch would get a K split over workgroups
-                                                                    //  instead of the skinny kernel, the answer must be row-major)
+    static int dummy; // (where a caller WITH scratch would get a K split over workgroups instead of the skinny kernel, the answer must be row-major)
+    const mixq::GemmParams probe = plan_probe(M, N, K, kNumOutliers, 1, gemm_scratch_bytes(M, N, K) != 0 ? &dummy : nullptr, nullptr);
     return mixq::gemm_takes_skinny(probe, mixq::EPI_DEQUANT) ? MIXQ_QA_FRAGMENT_MAJOR : MIXQ_QA_ROW_MAJOR;
 }
 
@@ -859,11 +866,10 @@ int mixq_gemm_mixed_layout(const int8_t* qA, const int8_t* W, const void* sA, co
     bool resolved = false;
     if (qa_layout == MIXQ_QA_FRAGMENT_MAJOR) {
         if (O > kNumOutliers || M <= 0 || N <= 0 || K <= 0 || !W) return MIXQ_E_SHAPE;
-        mixq::GemmParams probe{};
-        probe.M = M, probe.N = N, probe.K = K, probe.O = O, probe.a_frag = 1, probe.B = W;
-        probe.b_image = img = mixq::resolve_weight_image(W, N, K, static_cast<hipStream_t>(stream));
+        img = mixq::resolve_weight_image(W, N, K, static_cast<hipStream_t>(stream));
         resolved = true;
-        probe.splitk_ws = (scratch && scratch_bytes >= gemm_scratch_bytes(M, N, K) && gemm_scratch_bytes(M, N, K)) ? scratch : nullptr;
+        const size_t need = gemm_scratch_bytes(M, N, K);
+        const mixq::GemmParams probe = plan_probe(M, N, K, O, 1, scratch && need && scratch_bytes >= need ? scratch : nullptr, img);
         if (!mixq::gemm_takes_skinny(probe, mixq::EPI_DEQUANT)) return MIXQ_E_SHAPE; // (the image has ONE reader)
     }
     return gemm_mixed_impl(qA, W, sA, sW, fpA, fpW, Out, M, N, K, O, scratch, scratch_bytes, stream, qa_layout, img, resolved);
@@ -974,17 +980,19 @@ int mixq_w8a16_gemm_forward(const void* input, const uint8_t* weight, const void
 }
 
 // ------------------------------------------------------------------------------------------- enqueue ----
-// decode batches that the weight-streaming skinny GEMM serves: the quantiser writes qA in that kernel's MFMA fragment order (1), else 0
-static int enqueue_qa_frag(int64_t M, int64_t N, int64_t K, void* scratch, const void* W, const void* img)
+// The plan of one mixq_enqueue call's GEMM, and in *a_frag the qA layout its quantiser writes: decode batches that the weight-streaming
+// skinny GEMM serves get qA in that kernel's MFMA fragment order (1), every other call row-major (0)
+static mixq::GemmPlan enqueue_plan(int64_t M, int64_t N, int64_t K, int epi, void* scratch, const void* img, int* a_frag)
 {
-    if (!(M <= 64 && K % 16 == 0 && N % 16 == 0 && mixq::qa_frag_enabled() && mixq::quant_frag_layout_supported((int)M, (int)K))) return 0;
-    mixq::GemmParams probe{};
-    probe.M = (int)M, probe.N = (int)N, probe.K = (int)K, probe.O = kNumOutliers;
-    probe.splitk_ws = scratch;
-    probe.B = static_cast<const int8_t*>(W);
-    probe.b_image = img; // (a registered weight image widens the skinny kernel's range)
-    probe.a_frag = 1;    // ("if the quantiser writes the fragment-major image, does the skinny kernel take the problem?")
-    return mixq::gemm_takes_skinny(probe, mixq::EPI_DEQUANT) ? 1 : 0;
+    const bool may = M <= 64 && K % 16 == 0 && N % 16 == 0 && mixq::qa_frag_enabled() && mixq::quant_frag_layout_supported((int)M, (int)K);
+    mixq::GemmParams probe = plan_probe((int)M, (int)N, (int)K, kNumOutliers, may ? 1 : 0, scratch, img);
+    mixq::GemmPlan plan = mixq::plan_gemm(probe, epi);
+    if (may && plan.family != mixq::GEMM_SKINNY) { // (the image has ONE reader: the row-major call's plan)
+        probe.a_frag = 0;
+        plan = mixq::plan_gemm(probe, epi);
+    }
+    *a_frag = probe.a_frag;
+    return plan;
 }
 
 static int enqueue_impl(const mixq_handle* h, const mixq_tensor_desc* inputDesc, const void* const* inputs,
@@ -1048,13 +1056,14 @@ static int enqueue_impl(const mixq_handle* h, const mixq_tensor_desc* inputDesc,
         //  instruction = one 1-KiB read -- was built and measured on one box: GEMM -0.3 %, quantiser +7.6 % (its row becomes 32
         //  scattered 128-byte stores), prefill tokens/s -0.35 %: docs/LAB_NOTEBOOK.md R3.10.)
         const void* img = M <= 64 ? mixq::resolve_weight_image(W, (int)N, (int)K, st) : nullptr; // (ONE lookup per call: probe and launch agree)
-        const int frag = enqueue_qa_frag(M, N, K, scratch, W, img);
+        int frag = 0;
+        const mixq::GemmPlan plan = enqueue_plan(M, N, K, mixed_epi(bias != nullptr, bf16), scratch, img, &frag); // (ONE plan per call: quantiser and GEMM agree)
         int rc = hip_rc(mixq::launch_quant_extract(const_cast<void*>(A), qA, sA, fpA, ind, (int)M, (int)K, kNumOutliers,
                                                    false, st, scratch, frag, bf16));
         if (rc != MIXQ_OK) return rc;
         if (ev_gemm_start && hipEventRecord(static_cast<hipEvent_t>(ev_gemm_start), st) != hipSuccess) return MIXQ_E_HIP;
         rc = gemm_mixed_impl(qA, W, sA, scale_b, fpA, fp_weight, Out, (int)M, (int)N, (int)K, kNumOutliers, scratch,
-                             scratch_bytes, stream, frag, img, true, bias, bf16);
+                             scratch_bytes, stream, frag, img, true, bias, bf16, &plan);
         if (ev_gemm_stop && hipEventRecord(static_cast<hipEvent_t>(ev_gemm_stop), st) != hipSuccess) return MIXQ_E_HIP;
         return rc;
     }
@@ -1078,7 +1087,7 @@ static int enqueue_impl(const mixq_handle* h, const mixq_tensor_desc* inputDesc,
     return hip_rc(mixq::launch_w8a16_skinny_bias(A, q_weight, scaling_factors, Out, (int)M, (int)N, (int)K, bias, st));
 }
 
-// What mixq_enqueue would launch for a call with M rows on an [N, K] layer, as text (host only, no GPU needed; include/mixq.h).
+// The plan mixq_enqueue executes for a call with M rows on an [N, K] layer, as text (host only, no GPU needed; include/mixq.h).
 int mixq_describe_plan(int64_t M, int64_t N, int64_t K, int have_weight_image, char* buf, size_t len)
 {
     if (!buf || len == 0 || M <= 0 || N <= 0 || K <= 0 || M > INT32_MAX || N > INT32_MAX || K > INT32_MAX) return MIXQ_E_BADARG;
@@ -1089,13 +1098,9 @@ int mixq_describe_plan(int64_t M, int64_t N, int64_t K, int have_weight_image, c
     static int dummy_scratch, dummy_image;
     void* scratch = enqueue_scratch_bytes(M, N, K) ? &dummy_scratch : nullptr;
     const void* img = have_weight_image && M <= 64 && K % 64 == 0 && N % 16 == 0 ? &dummy_image : nullptr;
-    mixq::GemmParams p{};
-    p.M = (int)M, p.N = (int)N, p.K = (int)K, p.O = kNumOutliers;
-    p.splitk_ws = scratch;
-    p.b_image = img;
-    p.a_frag = enqueue_qa_frag(M, N, K, scratch, &dummy_image, img);
+    int frag;
     char plan[160];
-    mixq::describe_gemm_plan(p, mixq::EPI_DEQUANT, plan, sizeof plan);
+    mixq::describe_gemm_plan(enqueue_plan(M, N, K, mixq::EPI_DEQUANT, scratch, img, &frag), plan, sizeof plan);
     snprintf(buf, len, "quantise + extract (1 launch), then %s", plan);
     return MIXQ_OK;
 }

@@ -5,6 +5,7 @@
 
 #include <atomic>
 #include <string>
+#include <type_traits>
 
 namespace mixq {
 
@@ -48,6 +49,22 @@ enum { EPI_DEQUANT_BF16 = 6, EPI_DEQUANT_BIAS_BF16 = 7 };
 constexpr bool epi_has_silu(int epi) { return epi == EPI_DEQUANT_SILU || epi == EPI_DEQUANT_SILU_MUL; }
 constexpr bool epi_bf16(int epi) { return epi == EPI_DEQUANT_BF16 || epi == EPI_DEQUANT_BIAS_BF16; }
 constexpr bool epi_bias(int epi) { return epi == EPI_DEQUANT_BIAS || epi == EPI_DEQUANT_BIAS_BF16; }
+// f(std::integral_constant<int, EPI>{}) with the run-time `epi` as a compile-time constant: the six dequantising epilogues; any other
+// value is EPI_INT32 where the family has that build (INT32), else an error (and f is not instantiated for it)
+template <bool INT32, class F>
+inline hipError_t with_epi(int epi, F&& f)
+{
+    switch (epi) {
+    case EPI_DEQUANT: return f(std::integral_constant<int, EPI_DEQUANT>{});
+    case EPI_DEQUANT_SILU: return f(std::integral_constant<int, EPI_DEQUANT_SILU>{});
+    case EPI_DEQUANT_SILU_MUL: return f(std::integral_constant<int, EPI_DEQUANT_SILU_MUL>{});
+    case EPI_DEQUANT_BIAS: return f(std::integral_constant<int, EPI_DEQUANT_BIAS>{});
+    case EPI_DEQUANT_BF16: return f(std::integral_constant<int, EPI_DEQUANT_BF16>{});
+    case EPI_DEQUANT_BIAS_BF16: return f(std::integral_constant<int, EPI_DEQUANT_BIAS_BF16>{});
+    }
+    if constexpr (INT32) return f(std::integral_constant<int, EPI_INT32>{});
+    else return hipErrorInvalidValue;
+}
 
 // TP all-gather fused into the GEMM's store path (gemm_pp_kernels.hip, TP = true): every finished 32-row block of a wave
 // tile is written straight into this rank's column block of EVERY destination's [M, n_total] buffer (one-sided peer writes
@@ -67,7 +84,7 @@ struct TpEpilogue {
 };
 int tp_chunk_tile_rows(int M);     // tile rows per flag word for an M-row call: a multiple of the kernel's GROUP_M walk
 int tp_flag_words(int M);          // flag words a consumer must wait for = ceil(tile rows / chunk_tile_rows) <= kTpFlagWords
-bool gemm_tp_fused_supported(int M, int N, int K, int O); // launch_gemm would take the plain 256 x 256 ping-pong kernel
+bool gemm_tp_fused_supported(int M, int N, int K, int O); // the plan of the operator's call is the plain 256 x 256 ping-pong kernel
 
 struct GemmParams {
     const int8_t* A;      // qA [M,K]
@@ -100,46 +117,65 @@ struct GemmParams {
     const uint16_t* bias; // fp16 [N] of EPI_DEQUANT_BIAS (bf16 [N] of EPI_DEQUANT_BIAS_BF16) (added once, by whoever runs the final epilogue of an element), else null
 };
 
-hipError_t launch_gemm(const GemmParams& p, int epi, hipStream_t st);
-void describe_gemm_plan(const GemmParams& p, int epi, char* buf, size_t len); // what launch_gemm would launch, as text (host only)
-int gemm_deep_factor(int M, int N, int K, bool have_scratch);                 // workgroups per 128 x 128 tile of the deep form, 0: not taken
-int skinny_weight_route(int a_frag, bool image, int M, int N, int K);         // GemmParams::b_frag the skinny launcher would set
+// What one int8 GEMM call launches: decided once by plan_gemm (gemm_plan.hip: the ladder of DESIGN.md §4), read by launch_gemm, the
+// family launchers, describe_gemm_plan and every selection question of the API layer.  A plain value; fields of other families are 0.
+enum { GEMM_TILES = 0, GEMM_SKINNY, GEMM_DEEP, GEMM_PP_ABLATE, GEMM_PP128, GEMM_PP_SPLITK, GEMM_PP };
+enum { kTileCfgXs32 = 24, kTileCfgXs64 = 25 }; // GemmPlan::cfg of the two-barrier tiles with K split over workgroups (0..23: launch_gemm_tiles)
+struct GemmPlan {
+    int family;        // GEMM_*
+    int xs;            // workgroups per tile along K: deep form 1 / 2 / 4 / 8, 256 x 256 split 2 / 4 / 8, two-barrier tiles 2..16; else 0
+    int solo;          // GEMM_PP_SPLITK: leading tiles that are not split
+    int cfg;           // GEMM_TILES: tile configuration; GEMM_PP_ABLATE: the ablation
+    int tile_m, tile_n, kgroups; // GEMM_TILES: the configuration's tile and K groups inside the workgroup (0: forced by knob 10 + i)
+    int deep_build;    // GEMM_DEEP: 0 = 4 waves x 64 x 64, 1 = 8 waves x 64 x 32 (4 stages), 2 = 8 waves, 5 stages, 3 = the mid kernel (gemm_mid_kernels.hip)
+    bool deep_early;   // GEMM_DEEP builds 0..2: measurement -- every wave issues its slice copies before its MFMAs
+    int mid_bn;        // build 3: tile width 128 | 96
+    bool mid_rot;      // build 3: tile rows start at different K slices
+    bool qa_frag;      // GEMM_SKINNY: qA is the fragment-major image
+    int skinny_kw, skinny_abl;      // GEMM_SKINNY: K-split waves 4 / 8 / 16; measurement ablation or 0
+    int skinny_route, skinny_tiles; // GEMM_SKINNY: GemmParams::b_frag (skinny_weight_route); 16-column feature tiles per workgroup, 1 | 2
+    bool skinny_nt;    // GEMM_SKINNY route 3: non-temporal weight loads
+    const char* name;  // what last_gemm_kernel reports (null: left as it is)
+};
+GemmPlan plan_gemm(const GemmParams& p, int epi); // pure host function; without a device num_cus() answers 256
+hipError_t launch_gemm(const GemmParams& p, int epi, hipStream_t st, const GemmPlan* planned = nullptr); // planned: plan_gemm(p, epi) the caller already holds
+void describe_gemm_plan(const GemmPlan& plan, char* buf, size_t len); // the plan as text (host only)
+hipError_t launch_gemm_tiles(const GemmParams& p, int epi, const GemmPlan& plan, hipStream_t st); // two-barrier tiles (gemm_kernels.hip)
+void set_tile_nt(int mode); // measurement knob 1290 by rule (default) / 1291 never / 1292 always: non-temporal weight copies on a single tile row
+int skinny_weight_route(int a_frag, bool image, int M, int N, int K);         // GemmParams::b_frag of the skinny launch
+bool skinny_runs_nontemporal(int N, int K);                                   // that route 3 loads non-temporally
 hipError_t launch_gemm_pp(const GemmParams& p, int epi, hipStream_t st);  // 256x256 ping-pong schedule
 hipError_t launch_gemm_pp128(const GemmParams& p, int epi, hipStream_t st);
 hipError_t launch_gemm_pp_tp(const GemmParams& p, hipStream_t st); // EPI_DEQUANT (EPI_DEQUANT_BIAS when p.bias) with p.tp.ndst destinations instead of p.D
 // D[M,N] fp16 = A[M,K] B[N,K]^T, fp16 operands (K % 8 == 0, N % 8 == 0, 16-byte aligned rows), fp32 accumulation
 hipError_t launch_gemm_f16_pp(const void* A, const void* B, void* D, int M, int N, int K, const void* zeros, hipStream_t st);
 hipError_t launch_gemm_f16_pp128(const void* A, const void* B, void* D, int M, int N, int K, const void* zeros, hipStream_t st); // 128 x 256 tiles // 128x256 ping-pong schedule (mid-size problems)
-bool gemm_pp128_wins(int M, int N, int K); // launch_gemm's rule for taking the 128x256 tiles (then no K split, no scratch)
+bool gemm_pp128_wins(int M, int N, int K); // the rule for taking the 128x256 tiles (then no K split, no scratch)
 constexpr size_t kSplitkWordsBytes = 16384; // hand-over words (64 B per tile) of up to 256 split tiles, at the start of the scratch
 struct SplitPlan {
     int s;    // workgroups per split tile: 0 (no split form for this shape) / 2 / 4 / 8
     int solo; // leading tiles (whole waves) computed by one workgroup each, inside the same launch
 };
 SplitPlan gemm_splitk_plan(int M, int N, int K);
-int gemm_splitk_factor(int M, int N, int K);              // = plan.s
 size_t gemm_splitk_workspace_size(int M, int N, int K);   // 0: the shape does not use the split form (or it is off)
 size_t gemm_splitk_workspace_bound();                     // max of the above over all shapes (for workspace sizing)
-hipError_t launch_gemm_pp_splitk(const GemmParams& p, int epi, hipStream_t st);
+hipError_t launch_gemm_pp_splitk(const GemmParams& p, int epi, const GemmPlan& plan, hipStream_t st);
 void set_splitk_patience(unsigned ticks); // test knob: 0 = every workgroup but the last arriver defers at once
 void set_splitk_force(int v); // -1 automatic (default), 0 off, 2 / 4: that factor wherever the shape allows it
 // the same idea for the small-tile kernels with in-workgroup split (gemm_kernels.hip, XS): few tiles, long K
-int gemm_xsplit_factor(int M, int N, int K);              // 0 / 2 / 4 / 8 / 16
 size_t gemm_xsplit_workspace_size(int M, int N, int K);
 size_t gemm_xsplit_workspace_bound();
-void set_xsplit_force(int v); // -1 automatic (default), 0 off, 2 / 4 / 8 / 16 forced
 // mid-M deep form (gemm_kernels.hip): 128 x 128 tiles, 4 stages in flight, K split over 1 / 2 / 4 / 8 workgroups per tile
-bool gemm_deep_takes(int M, int N, int K, bool have_scratch);
 size_t gemm_deep_workspace_size(int M, int N, int K); // 0: the form is not used for this shape, or needs no scratch
-void set_deep_force(int v);
-hipError_t launch_gemm_deep(const GemmParams& p, int epi, hipStream_t st);
+hipError_t launch_gemm_deep(const GemmParams& p, int epi, const GemmPlan& plan, hipStream_t st);
 // round-6 schedule of the same tiles (gemm_mid_kernels.hip): 2 copy-only waves + 8 compute waves, one barrier per pair of slices; p.xsplit workgroups per tile
-hipError_t launch_gemm_mid(const GemmParams& p, int epi, hipStream_t st);
+hipError_t launch_gemm_mid(const GemmParams& p, int epi, const GemmPlan& plan, hipStream_t st);
 void set_mid_rot(int mode);  // measurement knob 1413 (default: 3 = by rule) / 1411 (0 = never) / 1410 (1 = unsplit tiles) / 1412 (2 = always)
 void set_mid_bn(int mode);   // measurement knob 1430 (default: 0 = by rule) / 1431 (1 = 128-wide tiles always)
-int gemm_mid_tile_width(int M, int N, int xsplit); // 128 | 96: the tile width launch_gemm_mid takes
+int gemm_mid_tile_width(int M, int N, int xsplit); // 128 | 96: the tile width of the mid kernel
+bool gemm_mid_rotated_walk(int M, int xsplit);     // its tile rows start at different K slices
 bool gemm_skinny_supported(const GemmParams& p);
-hipError_t launch_gemm_skinny(const GemmParams& p, int epi, hipStream_t st); // M <= 64: GEMV-like, HBM-bound on W
+hipError_t launch_gemm_skinny(const GemmParams& p, int epi, const GemmPlan& plan, hipStream_t st); // M <= 64: GEMV-like, HBM-bound on W
 hipError_t launch_gemm_pp_ablate(const GemmParams& p, int abl, hipStream_t st);  // timing experiments only
 void set_gemm_variant(int v);
 bool w8a16_skinny_takes(int M, int N, int K); // the fpA_intB skinny form serves this shape (w8a16_gemm_kernels.hip)
@@ -154,14 +190,8 @@ hipError_t launch_w8a16_skinny_bf16(const void* A, const uint8_t* Wq, const void
 //   256-row form | 200 / 201 / 202 two-pass form automatic / never / always, 203 / 204 its second pass on 256- / 128-row tiles
 //   | 300 / 301 skinny form automatic / off, 302..305 one of its shapes | 306 / 307 / 308 1..4 tokens through the skinny form
 //   always / never / automatic;  `ks`: -2 keep, -1 automatic, n = workgroups per tile along K.
-// fpA_intB measurement / test knobs (mixq_debug_set_gemm_variant 80..89, 831..834, 840..844, 850..858, 800 + ABL); `form`:
-//   -1 everything automatic | 0 narrow form | 1..4 wide form with 32 / 64 / 128 / 256-row tiles | 100 + ABL ablation of the
-//   256-row form | 200 / 201 / 202 two-pass form automatic / never / always, 203 / 204 its second pass on 256- / 128-row tiles
-//   | 300 / 301 skinny form automatic / off, 302..305 one of its shapes | 306 / 307 / 308 1..4 tokens through the skinny form
-//   always / never / automatic;  `ks`: -2 keep, -1 automatic, n = workgroups per tile along K.
 void set_wo_force(int form, int ks);
 const char* last_gemm_kernel(); // kernel family launch_gemm chose last (reporting only)
-void set_skinny_kw(int kw); // measurement knob: K-split width of the skinny kernel (0 = auto)
 void set_skinny_nt(int nt);
 void set_skinny_wrows(int on); // knob 884 on (default) / 885 off: row-major weights read in 256-byte runs (gemm_skinny_kernels.hip WFRAG == 3)
 void set_skinny_wfrag(int mode); // knob 880 automatic | 881 weight images with plain loads | 882 with non-temporal loads | 883 images ignored
@@ -186,9 +216,8 @@ hipError_t launch_quant_extract(void* A, int8_t* qA, void* sA, void* fpA, const 
 void set_quant_block_rows(int m); // measurement knob 1300 (rules) / 1301..1312 (64 << n rows)
 int quant_block_rows(int nvec, bool norm_producer); // rows up to which a whole 256-thread block takes one row of nvec 16-byte vectors
 bool quant_frag_layout_supported(int M, int K);   // the quantiser can write the fragment-major image for this shape
-bool gemm_takes_skinny(const GemmParams& p, int epi);
+bool gemm_takes_skinny(const GemmParams& p, int epi); // the plan of this problem is gemm_skinny_kernel
 bool qa_frag_enabled(); // test knob 890 / 891 (default on)
-bool probe_a2();        // timing probe 898 / 899 // launch_gemm would run gemm_skinny_kernel on this problem
 void set_quant_stamp_buffer(void* device_u64_8_per_block); // measurement only (NULL in production)
 // Activation producers (quantisers, outlier gathers, the fused RMSNorm producer): name of the form the most recent launch took,
 // e.g. "quant_extract_kernel<TPR=64,MAXV=8,ZERO=1,FRAG=0> nt" (" nt": non-temporal qA stores).  Reporting only.

@@ -42,7 +42,7 @@ FAMILY = [("skinny", b"gemm_skinny_kernel"), ("deep", b"<DEEP>"), ("ping-pong 12
 
 
 def test_described_plan_is_what_enqueue_launches():
-    """mixq_describe_plan (host only) restates launch_gemm's decisions; here every cell of a grid over BASELINE.json's (N, K) x a ladder of
+    """mixq_describe_plan (host only) prints the plan that launch_gemm executes; here every cell of a grid over BASELINE.json's (N, K) x a ladder of
     row counts is really launched through mixq_enqueue and the family the library reports afterwards must be the one described."""
     import ctypes
     sys.path.insert(0, ROOT)
