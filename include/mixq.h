@@ -277,6 +277,31 @@ MIXQ_API int mixq_quant_extract_layout(int M, int K, void* A_f16, int8_t* qA, vo
 MIXQ_API int mixq_rmsnorm_extract_quant_layout(int M, int K, const void* x_f16, const void* gamma_f16, void* out_f16, float eps,
                                                const int32_t* ind, int len, void* outliers_f16, int8_t* q, void* scale_f16,
                                                int q_layout, void* stream);
+/* ---- the residual add in front of the norm, in the norm's pass (MI355X extension) --------------------------------------------
+ * A decoder block adds the residual right in front of every norm (MixQ/src/mixquant/modules/fused/block.py:32-33).  Each entry below
+ * is the named entry above run on h = x + residual, with h written to h_f16 -- one launch and one pass over [M, K] instead of two:
+ *   h[m,k] = fp16_rn(float(x[m,k]) + float(residual[m,k]))     one rounding: the correctly rounded fp16 sum
+ *   mixq_add_rmsnorm                      = mixq_rmsnorm(h)
+ *   mixq_add_rmsnorm_extract_quant_layout = mixq_rmsnorm_extract_quant_layout(h)
+ *   mixq_add_rmsnorm_extract_quant4       = mixq_rmsnorm_extract_quant4(h)
+ * The norm sees the ROUNDED fp16 h, not the fp32 sum, and runs in the form (threads per row, vectors per lane, grid) the named entry
+ * takes for the same (M, K, q_layout): every output -- h, out, outliers, q, scale -- is BIT-IDENTICAL to an fp16 add followed by the
+ * corresponding mixq_rmsnorm* call (NaN payloads of the add aside).
+ * Aliasing: h_f16 may be the same pointer as x_f16 or as residual_f16 (the in-place update of the residual stream: every element is
+ * read before it is written, by the thread that writes it); a partial overlap is undefined; h_f16 == out_f16 is MIXQ_E_BADARG.
+ * x, residual and h are fp16 [M, K], 16-byte aligned (MIXQ_E_ALIGN), required when M > 0 (MIXQ_E_BADARG); every other argument and
+ * every other code as for the named entry, in the same order (MIXQ_E_BADARG, then MIXQ_E_SHAPE: K % 8, K > 32768, a fragment-major
+ * image for an unsupported shape, then MIXQ_E_ALIGN).  Every refusal happens before anything is launched; M == 0 returns MIXQ_OK
+ * without touching the device.  Asynchronous on `stream`, no allocation.  mixq_debug_last_producer_kernel reports these launches
+ * as the named entry's form with ",ADD=1" behind FRAG: "rmsnorm_quant_kernel<TPR=256,MAXV=2,QUANT=8,FRAG=0,ADD=1>". */
+MIXQ_API int mixq_add_rmsnorm(int M, int K, const void* x_f16, const void* residual_f16, void* h_f16, const void* gamma_f16,
+                              void* out_f16, float eps, void* stream);
+MIXQ_API int mixq_add_rmsnorm_extract_quant_layout(int M, int K, const void* x_f16, const void* residual_f16, void* h_f16,
+                                                   const void* gamma_f16, void* out_f16, float eps, const int32_t* ind, int len,
+                                                   void* outliers_f16, int8_t* q, void* scale_f16, int q_layout, void* stream);
+MIXQ_API int mixq_add_rmsnorm_extract_quant4(int M, int K, const void* x_f16, const void* residual_f16, void* h_f16,
+                                             const void* gamma_f16, void* out_f16, float eps, const int32_t* ind, int len,
+                                             void* outliers_f16, uint8_t* q_packed, void* scale_f16, void* stream);
 /* int8FusedDequantize / ...Silu / ...SiluMul (epilogue 0 / 1 / 3) on a qA image of the given layout; mul NULL unless epilogue 3 */
 MIXQ_API int mixq_int8_fused_dequantize_layout(const int8_t* A, const int8_t* B, const void* scale_row, const void* scale_col,
                                                const void* y, const void* mul, void* D, int M, int N, int K, int epilogue,
@@ -543,14 +568,15 @@ MIXQ_API const char* mixq_debug_last_gemm_kernel(void);
 /* Reporting only: the form the most recent activation-producer launch of this process took -- kernel, threads per row (TPR),
  * 16-byte vectors per lane (MAXV), outlier zeroing (ZERO) or quantisation (QUANT), fragment-major qA (FRAG), " nt" when the qA
  * stores are non-temporal -- e.g. "quant_extract_kernel<TPR=64,MAXV=8,ZERO=1,FRAG=0>", "quant_extract_long_kernel<ZERO=0>",
- * "rmsnorm_quant_kernel<TPR=256,MAXV=2,QUANT=4,FRAG=0>", "quant4_rows_kernel". */
+ * "rmsnorm_quant_kernel<TPR=256,MAXV=2,QUANT=4,FRAG=0>", "quant4_rows_kernel".  The mixq_add_rmsnorm* launches (residual add in the
+ * norm's pass) carry ",ADD=1" behind FRAG: "rmsnorm_quant_kernel<TPR=64,MAXV=8,QUANT=8,FRAG=0,ADD=1> nt". */
 MIXQ_API const char* mixq_debug_last_producer_kernel(void);
 MIXQ_API const char* mixq_version(void);
 /* ABI revision of THIS header.  It is bumped whenever an exported entry changes its argument list in place (revision 3: the
  * mixq_tp_buffer_alloc / mixq_tp_push_columns / mixq_tp_wait signatures of round 3), so that a host built against an older
  * header can refuse to run instead of passing shifted arguments: `if (mixq_abi_version() != MIXQ_ABI_VERSION) fail`.  The
  * reference-named entries (initOpenAiTritonPlugins, the plugin lifecycle, mixq_enqueue) have not changed since revision 1.
- * Revision 5 adds entries only (mixq_enqueue_bias, mixq_enqueue_tp_bias, mixq_gemm_mixed_bias). */
+ * Revision 5 adds entries only (mixq_enqueue_bias, mixq_enqueue_tp_bias, mixq_gemm_mixed_bias; later, still 5: mixq_add_rmsnorm*). */
 #define MIXQ_ABI_VERSION 5
 MIXQ_API int mixq_abi_version(void);
 MIXQ_API const char* mixq_error_string(int code);

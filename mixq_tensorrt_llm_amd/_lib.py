@@ -131,6 +131,9 @@ SIGNATURES = {
     "mixq_qa_bytes": (ctypes.c_size_t, [_i, _i, _i]),
     "mixq_quant_extract_layout": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "mixq_rmsnorm_extract_quant_layout": (_i, [_i, _i, _vp, _vp, _vp, ctypes.c_float, _vp, _i, _vp, _vp, _vp, _i, _vp]),
+    "mixq_add_rmsnorm": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp, ctypes.c_float, _vp]),
+    "mixq_add_rmsnorm_extract_quant_layout": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp, ctypes.c_float, _vp, _i, _vp, _vp, _vp, _i, _vp]),
+    "mixq_add_rmsnorm_extract_quant4": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp, ctypes.c_float, _vp, _i, _vp, _vp, _vp, _vp]),
     "mixq_int8_fused_dequantize_layout": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "mixq_gemm_mixed_layout": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, ctypes.c_size_t, _vp]),
     "mixq_gemm_s8s8s32": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),

@@ -513,6 +513,50 @@ int mixq_rmsnorm_extract_quant4(int M, int K, const void* x, const void* gamma, 
                                              M, K, len, 4, static_cast<hipStream_t>(stream)));
 }
 
+// ---- the residual add in front of the norm, in the norm's pass (MI355X extension): checks as the entries above, in their order ----
+int mixq_add_rmsnorm(int M, int K, const void* x, const void* residual, void* h, const void* gamma, void* out, float eps, void* stream)
+{
+    if (M < 0 || K <= 0 || (M > 0 && (!x || !residual || !h || !gamma || !out)) || (h && h == out)) return MIXQ_E_BADARG;
+    if (K % 8 || K > 32768) return MIXQ_E_SHAPE;
+    if (!aligned16(x) || !aligned16(residual) || !aligned16(h) || !aligned16(gamma) || !aligned16(out)) return MIXQ_E_ALIGN;
+    if (M == 0) return MIXQ_OK;
+    return hip_rc(mixq::launch_rmsnorm_quant(x, gamma, out, nullptr, nullptr, nullptr, nullptr, eps, M, K, 0, 0,
+                                             static_cast<hipStream_t>(stream), 0, residual, h));
+}
+
+int mixq_add_rmsnorm_extract_quant_layout(int M, int K, const void* x, const void* residual, void* h, const void* gamma, void* out,
+                                          float eps, const int32_t* ind, int len, void* outliers, int8_t* q, void* scale, int q_layout,
+                                          void* stream)
+{
+    const bool frag = q_layout == MIXQ_QA_FRAGMENT_MAJOR;
+    if (q_layout != MIXQ_QA_ROW_MAJOR && !frag) return MIXQ_E_BADARG;
+    if (M < 0 || K <= 0 || len < 0 || (M > 0 && (!x || !residual || !h || !gamma || !out || !q || !scale)) || (h && h == out))
+        return MIXQ_E_BADARG;
+    if (len > 0 && (!ind || !outliers)) return MIXQ_E_BADARG;
+    if (K % 8 || K > 32768 || (frag && M > 0 && !mixq::quant_frag_layout_supported(M, K))) return MIXQ_E_SHAPE;
+    if (!aligned16(x) || !aligned16(residual) || !aligned16(h) || !aligned16(gamma) || !aligned16(out) ||
+        (reinterpret_cast<uintptr_t>(q) & (frag ? 15u : 7u)))
+        return MIXQ_E_ALIGN;
+    if (M == 0) return MIXQ_OK;
+    return hip_rc(mixq::launch_rmsnorm_quant(x, gamma, out, outliers, ind, q, scale, eps, M, K, len, 8,
+                                             static_cast<hipStream_t>(stream), frag ? 1 : 0, residual, h));
+}
+
+int mixq_add_rmsnorm_extract_quant4(int M, int K, const void* x, const void* residual, void* h, const void* gamma, void* out, float eps,
+                                    const int32_t* ind, int len, void* outliers, uint8_t* q_packed, void* scale, void* stream)
+{
+    if (M < 0 || K <= 0 || len < 0 || (M > 0 && (!x || !residual || !h || !gamma || !out || !q_packed || !scale)) || (h && h == out))
+        return MIXQ_E_BADARG;
+    if (len > 0 && (!ind || !outliers)) return MIXQ_E_BADARG;
+    if (K % 8 || K > 32768) return MIXQ_E_SHAPE;
+    if (!aligned16(x) || !aligned16(residual) || !aligned16(h) || !aligned16(gamma) || !aligned16(out) ||
+        (reinterpret_cast<uintptr_t>(q_packed) & 3u))
+        return MIXQ_E_ALIGN;
+    if (M == 0) return MIXQ_OK;
+    return hip_rc(mixq::launch_rmsnorm_quant(x, gamma, out, outliers, ind, reinterpret_cast<int8_t*>(q_packed), scale, eps, M, K, len,
+                                             4, static_cast<hipStream_t>(stream), 0, residual, h));
+}
+
 // The GemmParams a selection question is asked with: mixq::plan_gemm reads the shape, the qA layout and WHETHER there is scratch and an image
 static mixq::GemmParams plan_probe(int M, int N, int K, int O, int a_frag, const void* scratch, const void* image)
 {

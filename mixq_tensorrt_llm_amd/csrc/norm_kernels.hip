@@ -20,13 +20,20 @@ constexpr int NBLOCK = 256;
 
 // QUANT: 0 = plain RMSNorm, 8 = int8 rows (scale amax/127), 4 = packed int4 rows (scale amax/7, layernorm.cu:201-290)
 // FRAG (QUANT == 8, decode batches): the int8 rows go out in the skinny GEMM's fragment-major order (quant_kernels.hip FRAG).
-template <int TPR, int MAXV, int QUANT, bool FRAG = false>
-__global__ __launch_bounds__(NBLOCK) void rmsnorm_quant_kernel(const uint16_t* __restrict__ X,
+// ADD: the residual add in front of the norm rides in the same pass -- h = fp16(x + R), rounded once, goes out to H and IS the
+// row from there on (sum of squares, normalisation, ... all see the rounded h), so every output has the bits of an fp16 add
+// followed by the ADD == false launch of the same form.  A lane holds its x and R vectors in registers before it stores h for
+// the same elements, and no lane reads another lane's: H may be X or R (not `out`).
+template <bool ADD> struct norm_row_ptr { typedef const uint16_t* __restrict__ type; };
+template <> struct norm_row_ptr<true> { typedef const uint16_t* type; }; // (H may alias it)
+
+template <int TPR, int MAXV, int QUANT, bool FRAG = false, bool ADD = false>
+__global__ __launch_bounds__(NBLOCK) void rmsnorm_quant_kernel(typename norm_row_ptr<ADD>::type X,
                                                                const uint16_t* __restrict__ gamma,
                                                                uint16_t* __restrict__ out, uint16_t* __restrict__ outl,
                                                                const int32_t* __restrict__ ind, int8_t* __restrict__ q,
                                                                uint16_t* __restrict__ scale, float eps, int M, int K,
-                                                               int O)
+                                                               int O, const uint16_t* R = nullptr, uint16_t* H = nullptr)
 {
     constexpr int RPB = NBLOCK / TPR;
     __shared__ float redf[NBLOCK / 64];
@@ -44,9 +51,11 @@ __global__ __launch_bounds__(NBLOCK) void rmsnorm_quant_kernel(const uint16_t* _
 
     // the row (and, for short rows, gamma) is requested FIRST: its round trip runs under the outlier-mask phase below (a
     // decode batch is a chain of latencies: the mask phase alone is an `ind` round trip + two barriers)
-    const uint4* __restrict__ src = reinterpret_cast<const uint4*>(X + (row_ok ? row : 0) * (int64_t)K);
+    const uint4* src = reinterpret_cast<const uint4*>(X + (row_ok ? row : 0) * (int64_t)K);
+    const uint4* res = ADD ? reinterpret_cast<const uint4*>(R + (row_ok ? row : 0) * (int64_t)K) : nullptr;
     const uint4* __restrict__ g4 = reinterpret_cast<const uint4*>(gamma);
     uint4 x[MAXV];
+    uint4 r[ADD ? MAXV : 1]; // the residual's vectors travel with the row's: both round trips run under the mask phase
     constexpr bool GPRE = MAXV <= 4; // gamma prefetched into registers (16 more VGPRs at most)
     uint4 gpre[GPRE ? MAXV : 1];
 #pragma unroll
@@ -54,6 +63,7 @@ __global__ __launch_bounds__(NBLOCK) void rmsnorm_quant_kernel(const uint16_t* _
         const int idx = v * TPR + t;
         x[v] = (row_ok && idx < nvec) ? src[idx] : make_uint4(0u, 0u, 0u, 0u);
         if (GPRE) gpre[v] = idx < nvec ? g4[idx] : make_uint4(0u, 0u, 0u, 0u);
+        if (ADD) r[v] = (row_ok && idx < nvec) ? res[idx] : make_uint4(0u, 0u, 0u, 0u);
     }
     if (QUANT) {
         for (int i = tid; i < mask_bytes / 4; i += NBLOCK) zmask[i] = 0u;
@@ -63,6 +73,22 @@ __global__ __launch_bounds__(NBLOCK) void rmsnorm_quant_kernel(const uint16_t* _
             if (c >= 0 && c < K) atomicOr(zmask + (c >> 5), 1u << (c & 31));
         }
         __syncthreads();
+    }
+    if (ADD) { // h = fp16(x + R): stored once, and the row from here on
+        uint4* hdst = reinterpret_cast<uint4*>(H + (row_ok ? row : 0) * (int64_t)K);
+#pragma unroll
+        for (int v = 0; v < MAXV; ++v) {
+            const int idx = v * TPR + t; // (lanes past the row hold 0 + 0)
+            const unsigned a[4] = {x[v].x, x[v].y, x[v].z, x[v].w};
+            const unsigned b[4] = {r[v].x, r[v].y, r[v].z, r[v].w};
+            unsigned o[4];
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                o[e] = (unsigned)hadd_bits((uint16_t)(a[e] & 0xffffu), (uint16_t)(b[e] & 0xffffu)) |
+                       ((unsigned)hadd_bits((uint16_t)(a[e] >> 16), (uint16_t)(b[e] >> 16)) << 16);
+            x[v] = make_uint4(o[0], o[1], o[2], o[3]);
+            if (row_ok && idx < nvec) hdst[idx] = x[v];
+        }
     }
 
     float ss = 0.f;
@@ -229,29 +255,36 @@ __global__ __launch_bounds__(NBLOCK) void rmsnorm_quant_kernel(const uint16_t* _
     }
 }
 
-// one name per instantiation and store form, built on its first launch (reporting only: mixq_debug_last_producer_kernel)
-template <int TPR, int MAXV, int QUANT, bool FRAG>
+// one name per instantiation and store form, built on its first launch (reporting only: mixq_debug_last_producer_kernel);
+// the ADD forms carry ",ADD=1" behind FRAG, the others keep the names they had
+static std::string norm_form_name(int tpr, int maxv, int quant, bool frag, bool add, bool nt)
+{
+    std::string n = producer_form_name("rmsnorm_quant_kernel", tpr, maxv, "QUANT", quant, frag, false);
+    if (add) n.insert(n.size() - 1, ",ADD=1"); // "...,FRAG=0,ADD=1>"
+    return n + (nt ? " nt" : "");
+}
+
+template <int TPR, int MAXV, int QUANT, bool FRAG, bool ADD>
 static void note_norm(bool nt)
 {
-    static const std::string n[2] = {producer_form_name("rmsnorm_quant_kernel", TPR, MAXV, "QUANT", QUANT, FRAG, false),
-                                     producer_form_name("rmsnorm_quant_kernel", TPR, MAXV, "QUANT", QUANT, FRAG, true)};
+    static const std::string n[2] = {norm_form_name(TPR, MAXV, QUANT, FRAG, ADD, false), norm_form_name(TPR, MAXV, QUANT, FRAG, ADD, true)};
     note_producer_kernel(n[nt ? 1 : 0].c_str());
 }
 
-template <int TPR, int MAXV>
+template <int TPR, int MAXV, bool ADD>
 static hipError_t launch_norm(const uint16_t* X, const uint16_t* gamma, uint16_t* out, uint16_t* outl,
                               const int32_t* ind, int8_t* q, uint16_t* scale, float eps, int M, int K, int O,
-                              int quant, hipStream_t st, int q_layout = 0)
+                              int quant, hipStream_t st, int q_layout, const uint16_t* R, uint16_t* H)
 {
     if constexpr (TPR == 256 && MAXV <= 8) {
         if (q_layout == 1 && quant == 8) {
             const size_t lds = (size_t)((K + 127) / 128) * 16 + (size_t)K * 2;
             static DeviceOnce oncef;
-            if (hipError_t e = ensure_dynamic_lds(rmsnorm_quant_kernel<TPR, MAXV, 8, true>, 160 * 1024 - 64, oncef); e != hipSuccess)
+            if (hipError_t e = ensure_dynamic_lds(rmsnorm_quant_kernel<TPR, MAXV, 8, true, ADD>, 160 * 1024 - 64, oncef); e != hipSuccess)
                 return e;
-            note_norm<TPR, MAXV, 8, true>(false);
-            hipLaunchKernelGGL((rmsnorm_quant_kernel<TPR, MAXV, 8, true>), dim3((unsigned)M), dim3(NBLOCK), lds, st, X, gamma, out,
-                               outl, ind, q, scale, eps, M, K, O);
+            note_norm<TPR, MAXV, 8, true, ADD>(false);
+            hipLaunchKernelGGL((rmsnorm_quant_kernel<TPR, MAXV, 8, true, ADD>), dim3((unsigned)M), dim3(NBLOCK), lds, st, X, gamma, out,
+                               outl, ind, q, scale, eps, M, K, O, R, H);
             return hipGetLastError();
         }
     }
@@ -262,52 +295,68 @@ static hipError_t launch_norm(const uint16_t* X, const uint16_t* gamma, uint16_t
         const size_t lds = (size_t)((K + 127) / 128) * 16 + (size_t)RPB * K * 2;
         // rows of 8192 x 4 waves need more than the default 64 KiB of dynamic LDS
         static DeviceOnce once8, once4;
-        if (hipError_t e = ensure_dynamic_lds(rmsnorm_quant_kernel<TPR, MAXV, 8>, 160 * 1024 - 64, once8); e != hipSuccess)
+        if (hipError_t e = ensure_dynamic_lds(rmsnorm_quant_kernel<TPR, MAXV, 8, false, ADD>, 160 * 1024 - 64, once8); e != hipSuccess)
             return e;
-        if (hipError_t e = ensure_dynamic_lds(rmsnorm_quant_kernel<TPR, MAXV, 4>, 160 * 1024 - 64, once4); e != hipSuccess)
+        if (hipError_t e = ensure_dynamic_lds(rmsnorm_quant_kernel<TPR, MAXV, 4, false, ADD>, 160 * 1024 - 64, once4); e != hipSuccess)
             return e;
-        if (quant == 4) note_norm<TPR, MAXV, 4, false>(false);
-        else note_norm<TPR, MAXV, 8, false>((int64_t)M * K >= ((int64_t)8 << 20)); // (the kernel's stream_out)
+        if (quant == 4) note_norm<TPR, MAXV, 4, false, ADD>(false);
+        else note_norm<TPR, MAXV, 8, false, ADD>((int64_t)M * K >= ((int64_t)8 << 20)); // (the kernel's stream_out)
         if (quant == 4)
-            hipLaunchKernelGGL((rmsnorm_quant_kernel<TPR, MAXV, 4>), grid, block, lds, st, X, gamma, out, outl, ind, q,
-                               scale, eps, M, K, O);
+            hipLaunchKernelGGL((rmsnorm_quant_kernel<TPR, MAXV, 4, false, ADD>), grid, block, lds, st, X, gamma, out, outl, ind, q,
+                               scale, eps, M, K, O, R, H);
         else
-            hipLaunchKernelGGL((rmsnorm_quant_kernel<TPR, MAXV, 8>), grid, block, lds, st, X, gamma, out, outl, ind, q,
-                               scale, eps, M, K, O);
+            hipLaunchKernelGGL((rmsnorm_quant_kernel<TPR, MAXV, 8, false, ADD>), grid, block, lds, st, X, gamma, out, outl, ind, q,
+                               scale, eps, M, K, O, R, H);
     } else {
-        note_norm<TPR, MAXV, 0, false>(false);
-        hipLaunchKernelGGL((rmsnorm_quant_kernel<TPR, MAXV, 0>), grid, block, 0, st, X, gamma, out, outl, ind, q,
-                           scale, eps, M, K, O);
+        note_norm<TPR, MAXV, 0, false, ADD>(false);
+        hipLaunchKernelGGL((rmsnorm_quant_kernel<TPR, MAXV, 0, false, ADD>), grid, block, 0, st, X, gamma, out, outl, ind, q,
+                           scale, eps, M, K, O, R, H);
     }
     return hipGetLastError();
 }
 
+// The form rules, once for both calls (ADD: with the residual add in front): the same (M, K, quant, q_layout) takes the same
+// TPR / MAXV / grid either way, so the reduction order -- and with it every bit -- is that of the unfused sequence.
+template <bool ADD>
+static hipError_t launch_rmsnorm_form(const uint16_t* x, const uint16_t* g, uint16_t* o, uint16_t* ol, const int32_t* ind, int8_t* q,
+                                      uint16_t* sc, float eps, int M, int K, int O, int quant, hipStream_t st, int q_layout,
+                                      const uint16_t* r, uint16_t* h)
+{
+    const int nvec = K / 8;
+    // Decode batches (few rows: the launch is a chain of latencies, not a stream): a whole 256-thread block per row, so that
+    // a row is ONE load round trip of 1-4 vectors per lane instead of 8-16 on a single wavefront -- the same rule as the
+    // quantiser's (quant_kernels.hip); 32 x 4096: 11.0 -> ~4.5 us for the fused producer (profiles/r03_small_m_timeline.txt)
+    if ((M <= quant_block_rows(nvec, true) || q_layout == 1) && nvec > 64 * 2) { // (round 5: at every size here -- the table in quant_kernels.hip)
+        if (nvec <= 256 * 2) return launch_norm<256, 2, ADD>(x, g, o, ol, ind, q, sc, eps, M, K, O, quant, st, q_layout, r, h);
+        if (nvec <= 256 * 4) return launch_norm<256, 4, ADD>(x, g, o, ol, ind, q, sc, eps, M, K, O, quant, st, q_layout, r, h);
+    }
+    if (nvec <= 64 * 2) return launch_norm<64, 2, ADD>(x, g, o, ol, ind, q, sc, eps, M, K, O, quant, st, 0, r, h);
+    if (nvec <= 64 * 4) return launch_norm<64, 4, ADD>(x, g, o, ol, ind, q, sc, eps, M, K, O, quant, st, 0, r, h);
+    if (nvec <= 64 * 8) return launch_norm<64, 8, ADD>(x, g, o, ol, ind, q, sc, eps, M, K, O, quant, st, 0, r, h);
+    if (nvec <= 64 * 16) return launch_norm<64, 16, ADD>(x, g, o, ol, ind, q, sc, eps, M, K, O, quant, st, 0, r, h);
+    if (nvec <= 256 * 8) return launch_norm<256, 8, ADD>(x, g, o, ol, ind, q, sc, eps, M, K, O, quant, st, q_layout, r, h);
+    if (nvec <= 256 * 16) return launch_norm<256, 16, ADD>(x, g, o, ol, ind, q, sc, eps, M, K, O, quant, st, 0, r, h);
+    return hipErrorInvalidValue;
+}
+
 // quant = 0: plain RMSNorm (only `out`), 8 / 4: fused producer.  hipErrorInvalidValue for rows longer than 32768.
+// residual / h_out (both or neither): the row is h = fp16(X + residual), written to h_out (which may be X or residual).
 hipError_t launch_rmsnorm_quant(const void* X, const void* gamma, void* out, void* outl, const int32_t* ind, int8_t* q,
-                                void* scale, float eps, int M, int K, int O, int quant, hipStream_t st, int q_layout)
+                                void* scale, float eps, int M, int K, int O, int quant, hipStream_t st, int q_layout,
+                                const void* residual, void* h_out)
 {
     if (q_layout != 0 && !(q_layout == 1 && quant == 8 && quant_frag_layout_supported(M, K))) return hipErrorInvalidValue;
+    if ((residual == nullptr) != (h_out == nullptr)) return hipErrorInvalidValue;
     if (M <= 0) return hipSuccess;
     const uint16_t* x = static_cast<const uint16_t*>(X);
     const uint16_t* g = static_cast<const uint16_t*>(gamma);
     uint16_t* o = static_cast<uint16_t*>(out);
     uint16_t* ol = static_cast<uint16_t*>(outl);
     uint16_t* sc = static_cast<uint16_t*>(scale);
-    const int nvec = K / 8;
-    // Decode batches (few rows: the launch is a chain of latencies, not a stream): a whole 256-thread block per row, so that
-    // a row is ONE load round trip of 1-4 vectors per lane instead of 8-16 on a single wavefront -- the same rule as the
-    // quantiser's (quant_kernels.hip); 32 x 4096: 11.0 -> ~4.5 us for the fused producer (profiles/r03_small_m_timeline.txt)
-    if ((M <= quant_block_rows(nvec, true) || q_layout == 1) && nvec > 64 * 2) { // (round 5: at every size here -- the table in quant_kernels.hip)
-        if (nvec <= 256 * 2) return launch_norm<256, 2>(x, g, o, ol, ind, q, sc, eps, M, K, O, quant, st, q_layout);
-        if (nvec <= 256 * 4) return launch_norm<256, 4>(x, g, o, ol, ind, q, sc, eps, M, K, O, quant, st, q_layout);
-    }
-    if (nvec <= 64 * 2) return launch_norm<64, 2>(x, g, o, ol, ind, q, sc, eps, M, K, O, quant, st);
-    if (nvec <= 64 * 4) return launch_norm<64, 4>(x, g, o, ol, ind, q, sc, eps, M, K, O, quant, st);
-    if (nvec <= 64 * 8) return launch_norm<64, 8>(x, g, o, ol, ind, q, sc, eps, M, K, O, quant, st);
-    if (nvec <= 64 * 16) return launch_norm<64, 16>(x, g, o, ol, ind, q, sc, eps, M, K, O, quant, st);
-    if (nvec <= 256 * 8) return launch_norm<256, 8>(x, g, o, ol, ind, q, sc, eps, M, K, O, quant, st, q_layout);
-    if (nvec <= 256 * 16) return launch_norm<256, 16>(x, g, o, ol, ind, q, sc, eps, M, K, O, quant, st);
-    return hipErrorInvalidValue;
+    if (residual)
+        return launch_rmsnorm_form<true>(x, g, o, ol, ind, q, sc, eps, M, K, O, quant, st, q_layout,
+                                         static_cast<const uint16_t*>(residual), static_cast<uint16_t*>(h_out));
+    return launch_rmsnorm_form<false>(x, g, o, ol, ind, q, sc, eps, M, K, O, quant, st, q_layout, nullptr, nullptr);
 }
 
 } // namespace mixq

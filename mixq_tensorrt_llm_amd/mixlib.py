@@ -17,7 +17,9 @@ __all__ = ["FindRowScale", "ExtractOutliersAndSetToZeros", "int8FusedDequantize"
            "int8_matrix_to_half", "w8_a16_gemm", "preprocess_weights", "mixq_linear", "int4FusedDequantize",
            "int4FusedDequantizeSilu", "unpack_int4_to_fp16", "unpack_int4_to_int8", "int8FusedDequantizeSiluMul",
            "layernorm_forward_cuda_extract_outliers_int4", "ExtractOutliers", "dequantizeInt8Silu", "mixlinear_forward",
-           "qa_layout", "qa_to_row_major", "QA_ROW_MAJOR", "QA_FRAGMENT_MAJOR", "WeightImage"]
+           "qa_layout", "qa_to_row_major", "QA_ROW_MAJOR", "QA_FRAGMENT_MAJOR", "WeightImage",
+           "add_layernorm_forward_cuda", "add_layernorm_forward_cuda_extract_outliers",
+           "add_layernorm_forward_cuda_extract_outliers_int4"]
 
 QA_ROW_MAJOR, QA_FRAGMENT_MAJOR = 0, 1   # include/mixq.h MIXQ_QA_*
 
@@ -408,6 +410,69 @@ def layernorm_forward_cuda_extract_outliers_int4(_input, _gamma, _out, eps, _ind
     _lib.check(_lib.load().mixq_rmsnorm_extract_quant4(m, c, _p(_input), _p(_gamma), _p(_out), ctypes.c_float(eps),
                                                        _p(_ind), n, _p(outl), _p(q), _p(scaleRow), _st(_input)),
                "layernorm_forward_cuda_extract_outliers_int4")
+    return [outl, q]
+
+
+def _add_operands(_input, _residual, h_out, what):
+    """The residual-add forms' row operands: same shape, fp16, contiguous; ``h_out`` None = in place into ``_residual``."""
+    h = _residual if h_out is None else h_out
+    for name, t in (("_input", _input), ("_residual", _residual), ("h_out", h)):
+        if t.dtype != torch.float16 or not t.is_contiguous():
+            raise ValueError(f"{what}: {name} must be a contiguous fp16 tensor (got {t.dtype}, contiguous={t.is_contiguous()})")
+        if t.shape != _input.shape:
+            raise ValueError(f"{what}: {name} has shape {tuple(t.shape)}, _input has {tuple(_input.shape)}")
+    return h
+
+
+@_on_tensor_device
+def add_layernorm_forward_cuda(_input, _residual, _gamma, _out, eps, h_out=None):
+    """MI355X extension (``mixq_add_rmsnorm``): ``layernorm_forward_cuda`` on h = _input + _residual (fp16, rounded once) in one
+    pass; h goes to ``h_out`` (None: in place into ``_residual``; it may also be ``_input``) and is returned.  Same bits as the
+    torch add followed by ``layernorm_forward_cuda``."""
+    h = _add_operands(_input, _residual, h_out, "add_layernorm_forward_cuda")
+    _dev(_input, _residual, h, _gamma, _out)
+    c = _input.shape[-1]
+    m = _input.numel() // c
+    _lib.check(_lib.load().mixq_add_rmsnorm(m, c, _p(_input), _p(_residual), _p(h), _p(_gamma), _p(_out), ctypes.c_float(eps),
+                                            _st(_input)), "add_layernorm_forward_cuda")
+    return h
+
+
+@_on_tensor_device
+def add_layernorm_forward_cuda_extract_outliers(_input, _residual, _gamma, _out, eps, _ind, scaleRow, q_layout=0, h_out=None):
+    """MI355X extension (``mixq_add_rmsnorm_extract_quant_layout``): ``layernorm_forward_cuda_extract_outliers`` on
+    h = _input + _residual in one pass; h goes to ``h_out`` (None: in place into ``_residual``).  Returns [outliers, quant]."""
+    h = _add_operands(_input, _residual, h_out, "add_layernorm_forward_cuda_extract_outliers")
+    _dev(_input, _residual, h, _gamma, _out, _ind, scaleRow)
+    c = _input.shape[-1]
+    m = _input.numel() // c
+    _rows_fit(scaleRow, m, "add_layernorm_forward_cuda_extract_outliers")
+    n = _ind.shape[0]
+    outl = torch.zeros((m, n), dtype=torch.float16, device=_input.device)
+    q = _alloc_q(m, c, q_layout, _input.device)
+    _lib.check(_lib.load().mixq_add_rmsnorm_extract_quant_layout(m, c, _p(_input), _p(_residual), _p(h), _p(_gamma), _p(_out),
+                                                                 ctypes.c_float(eps), _p(_ind), n, _p(outl), _p(q), _p(scaleRow),
+                                                                 q_layout, _st(_input)),
+               "add_layernorm_forward_cuda_extract_outliers")
+    return [outl, q]
+
+
+@_on_tensor_device
+def add_layernorm_forward_cuda_extract_outliers_int4(_input, _residual, _gamma, _out, eps, _ind, scaleRow, h_out=None):
+    """MI355X extension (``mixq_add_rmsnorm_extract_quant4``): the same with packed 4-bit rows (scale = amax / 7).
+    Returns [outliers fp16 [m,len], quant uint8 [m, c/2]]."""
+    h = _add_operands(_input, _residual, h_out, "add_layernorm_forward_cuda_extract_outliers_int4")
+    _dev(_input, _residual, h, _gamma, _out, _ind, scaleRow)
+    c = _input.shape[-1]
+    m = _input.numel() // c
+    _rows_fit(scaleRow, m, "add_layernorm_forward_cuda_extract_outliers_int4")
+    n = _ind.shape[0]
+    outl = torch.zeros((m, n), dtype=torch.float16, device=_input.device)
+    q = torch.empty((m, c // 2), dtype=torch.uint8, device=_input.device)
+    _lib.check(_lib.load().mixq_add_rmsnorm_extract_quant4(m, c, _p(_input), _p(_residual), _p(h), _p(_gamma), _p(_out),
+                                                           ctypes.c_float(eps), _p(_ind), n, _p(outl), _p(q), _p(scaleRow),
+                                                           _st(_input)),
+               "add_layernorm_forward_cuda_extract_outliers_int4")
     return [outl, q]
 
 

@@ -353,11 +353,15 @@ class FasterTransformerRMSNorm:
         self.cache = cache
         self.next_layer = None
 
-    @torch.no_grad()
-    def forward(self, x):
-        output = torch.empty_like(x)
+    def _produce(self, x, output, residual=None):
+        """The norm of ``x`` -- or, with ``residual``, of h = x + residual, written into ``residual`` in the same pass -- into
+        ``output``, quantised for ``next_layer`` (its bit width, outlier set and preferred int8 image) when there is one."""
+        add = residual is not None
         if self.next_layer is None:
-            mixlib.layernorm_forward_cuda(x, self.weight, output, self.variance_epsilon)
+            if add:
+                mixlib.add_layernorm_forward_cuda(x, residual, self.weight, output, self.variance_epsilon)
+            else:
+                mixlib.layernorm_forward_cuda(x, self.weight, output, self.variance_epsilon)
         elif self.next_layer.bit == 8:
             # decode batches: the int8 rows in the image the next layer's GEMM reads fastest (mixlib.qa_layout; the gate
             # projection that re-uses the cache has the same N).  A dynamic outlier set re-quantises row-major later.
@@ -367,14 +371,33 @@ class FasterTransformerRMSNorm:
             lay = mixlib.qa_layout(m, self.next_layer.out_features, c) if (n_out % 8 == 0 and n_out <= 128 and
                                                                             not self.next_layer.add_outliers) else 0
             self.cache.q_layout = lay
-            self.cache.activation_outliers, self.cache.q_xcache = mixlib.layernorm_forward_cuda_extract_outliers(
-                x, self.weight, output, self.variance_epsilon, self.next_layer.ind, self.cache.x_scale, lay)
+            if add:
+                self.cache.activation_outliers, self.cache.q_xcache = mixlib.add_layernorm_forward_cuda_extract_outliers(
+                    x, residual, self.weight, output, self.variance_epsilon, self.next_layer.ind, self.cache.x_scale, lay)
+            else:
+                self.cache.activation_outliers, self.cache.q_xcache = mixlib.layernorm_forward_cuda_extract_outliers(
+                    x, self.weight, output, self.variance_epsilon, self.next_layer.ind, self.cache.x_scale, lay)
         elif self.next_layer.bit == 4:
-            self.cache.activation_outliers, self.cache.q_xcache = mixlib.layernorm_forward_cuda_extract_outliers_int4(
-                x, self.weight, output, self.variance_epsilon, self.next_layer.ind, self.cache.x_scale)
+            if add:
+                self.cache.activation_outliers, self.cache.q_xcache = mixlib.add_layernorm_forward_cuda_extract_outliers_int4(
+                    x, residual, self.weight, output, self.variance_epsilon, self.next_layer.ind, self.cache.x_scale)
+            else:
+                self.cache.activation_outliers, self.cache.q_xcache = mixlib.layernorm_forward_cuda_extract_outliers_int4(
+                    x, self.weight, output, self.variance_epsilon, self.next_layer.ind, self.cache.x_scale)
         else:
             raise NotImplementedError
         return output
+
+    @torch.no_grad()
+    def forward(self, x):
+        return self._produce(x, torch.empty_like(x))
+
+    @torch.no_grad()
+    def forward_residual(self, x, residual):
+        """MI355X extension -- the block's ``h = residual + x`` (fused/block.py:32-33) in the norm's pass: returns
+        ``(forward(h), h)`` with h = fp16(x + residual) written into ``residual``'s storage.  The same bits as
+        ``residual += x; forward(residual)``, one launch and one pass over the hidden state less."""
+        return self._produce(x, torch.empty_like(x), residual), residual
 
     __call__ = forward
 
