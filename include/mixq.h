@@ -302,6 +302,31 @@ MIXQ_API int mixq_add_rmsnorm_extract_quant_layout(int M, int K, const void* x_f
 MIXQ_API int mixq_add_rmsnorm_extract_quant4(int M, int K, const void* x_f16, const void* residual_f16, void* h_f16,
                                              const void* gamma_f16, void* out_f16, float eps, const int32_t* ind, int len,
                                              void* outliers_f16, uint8_t* q_packed, void* scale_f16, void* stream);
+/* ---- typed forms of the norm producer (MI355X extension): fp16 or bf16 rows -----------------------------------------------------
+ * The reference's norms are fp16 only (quantkernel/mix_cuda/layernorm/layernorm.cu:41-198 take half); bf16 checkpoints (Qwen2,
+ * Llama-3) need the same producer on bf16 rows in front of a bf16 call of the operator.  `type` is MIXQ_TYPE_HALF or MIXQ_TYPE_BF16
+ * and names the type of x, residual, h, gamma, out, outliers and scale; anything else returns MIXQ_E_TYPE before every other check.
+ * residual == NULL && h == NULL: no add (mixq_rmsnorm / mixq_rmsnorm_extract_quant_layout); both given: the residual add in the
+ * norm's pass (mixq_add_rmsnorm / mixq_add_rmsnorm_extract_quant_layout); exactly one of them NULL: MIXQ_E_BADARG.
+ * MIXQ_TYPE_HALF IS that entry: same bits, same codes in the same order, same launch.
+ * MIXQ_TYPE_BF16 takes the form (threads per row, vectors per lane, grid, reduction order) the fp16 entry takes for the same
+ * (M, K, q_layout), with IEEE fp32 arithmetic as written:
+ *   h[m,k]   = bf16_rn(float(x) + float(residual))                with a residual: torch's bf16 add; stored once, and the row from here on
+ *   rstd     = 1 / sqrt(sum_k float(row)^2 / K + eps)
+ *   out      = bf16_rn((float(row) * rstd) * float(gamma))        no clamp: bf16 has fp32's range (the +-64504 clamp guards fp16)
+ *   outliers[m,j] = out[m, ind[j]] (0 for ind[j] outside [0, K)); out[m, ind[j]] = 0
+ *   scale[m] = bf16_rn(float(amax) / 127)                         amax over the zeroed row, NaNs dropped, an all-NaN row gives NaN
+ *   q[m,k]   = sat[-127, 127](rint(float(out) / float(scale)))    a NaN quotient gives 0 -- the bf16 rules of mixq_enqueue's quantiser
+ * The quantiser sees the ROUNDED bf16 row: q and scale are an exact function of the bits of `out`, and the call is bit-identical
+ * to a bf16 norm followed by that quantiser.  Arguments, aliasing (h may be x or residual, never out), codes and their order
+ * (MIXQ_E_BADARG, then MIXQ_E_SHAPE: K % 8, K > 32768, a fragment-major image for an unsupported shape, then MIXQ_E_ALIGN) as for
+ * mixq_add_rmsnorm*; M == 0 returns MIXQ_OK without touching the device.  Asynchronous on `stream`, no allocation, capturable.
+ * mixq_debug_last_producer_kernel reports a bf16 launch as the fp16 form's name + " [bf16]" (" nt" behind it where it applies). */
+MIXQ_API int mixq_rmsnorm_typed(int M, int K, const void* x, const void* residual, void* h, const void* gamma, void* out, float eps,
+                                int type, void* stream);
+MIXQ_API int mixq_rmsnorm_extract_quant_typed(int M, int K, const void* x, const void* residual, void* h, const void* gamma, void* out,
+                                              float eps, const int32_t* ind, int len, void* outliers, int8_t* q, void* scale,
+                                              int q_layout, int type, void* stream);
 /* int8FusedDequantize / ...Silu / ...SiluMul (epilogue 0 / 1 / 3) on a qA image of the given layout; mul NULL unless epilogue 3 */
 MIXQ_API int mixq_int8_fused_dequantize_layout(const int8_t* A, const int8_t* B, const void* scale_row, const void* scale_col,
                                                const void* y, const void* mul, void* D, int M, int N, int K, int epilogue,
@@ -309,6 +334,17 @@ MIXQ_API int mixq_int8_fused_dequantize_layout(const int8_t* A, const int8_t* B,
 MIXQ_API int mixq_gemm_mixed_layout(const int8_t* qA, const int8_t* W, const void* sA, const void* sW, const void* fpA,
                                     const void* fpW, void* Out, int M, int N, int K, int O, int qa_layout, void* scratch,
                                     size_t scratch_bytes, void* stream);
+/* mixq_gemm_mixed_layout by type (MI355X extension; the reference's GEMM is fp16 only, TsinghuaMixQPlugin.cpp:122-161): the consumer of
+ * what mixq_rmsnorm_extract_quant_typed writes.  `type` is MIXQ_TYPE_HALF or MIXQ_TYPE_BF16, anything else MIXQ_E_TYPE before every
+ * other check; bias ([N], 16-byte aligned) may be NULL.  MIXQ_TYPE_HALF IS mixq_gemm_mixed_layout, or, with a bias, mixq_gemm_mixed_bias
+ * on a qA image of the given layout.  MIXQ_TYPE_BF16: sA, fpA, fpW, bias and Out are bf16, sW stays fp16; the outlier product runs
+ * on the bf16 MFMA and is rounded to bf16, Out = bf16_rn(fma(acc, sW sA, P)), then one bf16 add of the bias -- the epilogue of a
+ * bf16 call of mixq_enqueue, and the kernel mixq_gemm_mixed_layout chooses for the shape.  O > 128 with bf16 or a bias is
+ * MIXQ_E_SHAPE; qa_layout as mixq_gemm_mixed_layout (fragment-major only where the skinny kernel serves the shape, else
+ * MIXQ_E_SHAPE).  Asynchronous, no allocation, capturable; scratch as mixq_gemm_mixed_scratch (may be NULL). */
+MIXQ_API int mixq_gemm_mixed_typed(const int8_t* qA, const int8_t* W, const void* sA, const void* sW, const void* fpA, const void* fpW,
+                                   const void* bias, void* Out, int M, int N, int K, int O, int qa_layout, int type, void* scratch,
+                                   size_t scratch_bytes, void* stream);
 /* MixLinear_GEMM.forward (MixQ/src/mixquant/modules/linear.py:163-286, bit = 8, static outlier set) as ONE call and TWO
  * launches: the reference makes four mixlib calls per linear here (ExtractOutliersAndSetToZeros, FindRowScale, torch.mm on the
  * outliers, int8FusedDequantize); a decode step is host-bound on those calls long before it is GPU-bound
@@ -569,14 +605,16 @@ MIXQ_API const char* mixq_debug_last_gemm_kernel(void);
  * 16-byte vectors per lane (MAXV), outlier zeroing (ZERO) or quantisation (QUANT), fragment-major qA (FRAG), " nt" when the qA
  * stores are non-temporal -- e.g. "quant_extract_kernel<TPR=64,MAXV=8,ZERO=1,FRAG=0>", "quant_extract_long_kernel<ZERO=0>",
  * "rmsnorm_quant_kernel<TPR=256,MAXV=2,QUANT=4,FRAG=0>", "quant4_rows_kernel".  The mixq_add_rmsnorm* launches (residual add in the
- * norm's pass) carry ",ADD=1" behind FRAG: "rmsnorm_quant_kernel<TPR=64,MAXV=8,QUANT=8,FRAG=0,ADD=1> nt". */
+ * norm's pass) carry ",ADD=1" behind FRAG: "rmsnorm_quant_kernel<TPR=64,MAXV=8,QUANT=8,FRAG=0,ADD=1> nt"; bf16 launches " [bf16]" behind
+ * the name: "rmsnorm_quant_kernel<TPR=256,MAXV=2,QUANT=8,FRAG=0,ADD=1> [bf16]". */
 MIXQ_API const char* mixq_debug_last_producer_kernel(void);
 MIXQ_API const char* mixq_version(void);
 /* ABI revision of THIS header.  It is bumped whenever an exported entry changes its argument list in place (revision 3: the
  * mixq_tp_buffer_alloc / mixq_tp_push_columns / mixq_tp_wait signatures of round 3), so that a host built against an older
  * header can refuse to run instead of passing shifted arguments: `if (mixq_abi_version() != MIXQ_ABI_VERSION) fail`.  The
  * reference-named entries (initOpenAiTritonPlugins, the plugin lifecycle, mixq_enqueue) have not changed since revision 1.
- * Revision 5 adds entries only (mixq_enqueue_bias, mixq_enqueue_tp_bias, mixq_gemm_mixed_bias; later, still 5: mixq_add_rmsnorm*). */
+ * Revision 5 adds entries only (mixq_enqueue_bias, mixq_enqueue_tp_bias, mixq_gemm_mixed_bias; later, still 5: mixq_add_rmsnorm*,
+ * mixq_rmsnorm_typed, mixq_rmsnorm_extract_quant_typed, mixq_gemm_mixed_typed). */
 #define MIXQ_ABI_VERSION 5
 MIXQ_API int mixq_abi_version(void);
 MIXQ_API const char* mixq_error_string(int code);

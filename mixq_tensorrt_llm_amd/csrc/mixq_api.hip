@@ -557,6 +557,47 @@ int mixq_add_rmsnorm_extract_quant4(int M, int K, const void* x, const void* res
                                              4, static_cast<hipStream_t>(stream), 0, residual, h));
 }
 
+// ---- typed forms of the norm producer (MI355X extension): fp16 = the entries above, bf16 = their checks in their order on bf16 rows ----
+static bool norm_type_ok(int type) { return type == MIXQ_TYPE_HALF || type == MIXQ_TYPE_BF16; }
+
+int mixq_rmsnorm_typed(int M, int K, const void* x, const void* residual, void* h, const void* gamma, void* out, float eps, int type,
+                       void* stream)
+{
+    if (!norm_type_ok(type)) return MIXQ_E_TYPE;
+    if ((residual == nullptr) != (h == nullptr)) return MIXQ_E_BADARG;
+    if (type == MIXQ_TYPE_HALF)
+        return residual ? mixq_add_rmsnorm(M, K, x, residual, h, gamma, out, eps, stream) : mixq_rmsnorm(M, K, x, gamma, out, eps, stream);
+    if (M < 0 || K <= 0 || (M > 0 && (!x || !gamma || !out)) || (h && h == out)) return MIXQ_E_BADARG;
+    if (K % 8 || K > 32768) return MIXQ_E_SHAPE;
+    if (!aligned16(x) || !aligned16(residual) || !aligned16(h) || !aligned16(gamma) || !aligned16(out)) return MIXQ_E_ALIGN;
+    if (M == 0) return MIXQ_OK;
+    return hip_rc(mixq::launch_rmsnorm_quant(x, gamma, out, nullptr, nullptr, nullptr, nullptr, eps, M, K, 0, 0,
+                                             static_cast<hipStream_t>(stream), 0, residual, h, true));
+}
+
+int mixq_rmsnorm_extract_quant_typed(int M, int K, const void* x, const void* residual, void* h, const void* gamma, void* out, float eps,
+                                     const int32_t* ind, int len, void* outliers, int8_t* q, void* scale, int q_layout, int type,
+                                     void* stream)
+{
+    if (!norm_type_ok(type)) return MIXQ_E_TYPE;
+    if ((residual == nullptr) != (h == nullptr)) return MIXQ_E_BADARG;
+    if (type == MIXQ_TYPE_HALF)
+        return residual ? mixq_add_rmsnorm_extract_quant_layout(M, K, x, residual, h, gamma, out, eps, ind, len, outliers, q, scale, q_layout,
+                                                                stream)
+                        : mixq_rmsnorm_extract_quant_layout(M, K, x, gamma, out, eps, ind, len, outliers, q, scale, q_layout, stream);
+    const bool frag = q_layout == MIXQ_QA_FRAGMENT_MAJOR;
+    if (q_layout != MIXQ_QA_ROW_MAJOR && !frag) return MIXQ_E_BADARG;
+    if (M < 0 || K <= 0 || len < 0 || (M > 0 && (!x || !gamma || !out || !q || !scale)) || (h && h == out)) return MIXQ_E_BADARG;
+    if (len > 0 && (!ind || !outliers)) return MIXQ_E_BADARG;
+    if (K % 8 || K > 32768 || (frag && M > 0 && !mixq::quant_frag_layout_supported(M, K))) return MIXQ_E_SHAPE;
+    if (!aligned16(x) || !aligned16(residual) || !aligned16(h) || !aligned16(gamma) || !aligned16(out) ||
+        (reinterpret_cast<uintptr_t>(q) & (frag ? 15u : 7u)))
+        return MIXQ_E_ALIGN;
+    if (M == 0) return MIXQ_OK;
+    return hip_rc(mixq::launch_rmsnorm_quant(x, gamma, out, outliers, ind, q, scale, eps, M, K, len, 8, static_cast<hipStream_t>(stream),
+                                             frag ? 1 : 0, residual, h, true));
+}
+
 // The GemmParams a selection question is asked with: mixq::plan_gemm reads the shape, the qA layout and WHETHER there is scratch and an image
 static mixq::GemmParams plan_probe(int M, int N, int K, int O, int a_frag, const void* scratch, const void* image)
 {
@@ -917,6 +958,31 @@ int mixq_gemm_mixed_layout(const int8_t* qA, const int8_t* W, const void* sA, co
         if (!mixq::gemm_takes_skinny(probe, mixq::EPI_DEQUANT)) return MIXQ_E_SHAPE; // (the image has ONE reader)
     }
     return gemm_mixed_impl(qA, W, sA, sW, fpA, fpW, Out, M, N, K, O, scratch, scratch_bytes, stream, qa_layout, img, resolved);
+}
+
+// the launcher-level fused GEMM by type: fp16 = mixq_gemm_mixed_layout (mixq_gemm_mixed_bias's checks in front when a bias is given),
+// bf16 = the same checks and the same kernel choice with the bf16 epilogues (sA, fpA, fpW, bias and Out bf16; sW fp16)
+int mixq_gemm_mixed_typed(const int8_t* qA, const int8_t* W, const void* sA, const void* sW, const void* fpA, const void* fpW,
+                          const void* bias, void* Out, int M, int N, int K, int O, int qa_layout, int type, void* scratch,
+                          size_t scratch_bytes, void* stream)
+{
+    if (type != MIXQ_TYPE_HALF && type != MIXQ_TYPE_BF16) return MIXQ_E_TYPE;
+    const bool bf16 = type == MIXQ_TYPE_BF16;
+    if (!bf16 && !bias) return mixq_gemm_mixed_layout(qA, W, sA, sW, fpA, fpW, Out, M, N, K, O, qa_layout, scratch, scratch_bytes, stream);
+    if (qa_layout != MIXQ_QA_ROW_MAJOR && qa_layout != MIXQ_QA_FRAGMENT_MAJOR) return MIXQ_E_BADARG;
+    if (bias && !aligned16(bias)) return MIXQ_E_ALIGN;
+    if (O > kNumOutliers) return MIXQ_E_SHAPE; // (one LDS pass of outlier columns: the bias and the bf16 epilogues take no addend)
+    const void* img = nullptr;
+    bool resolved = false;
+    if (qa_layout == MIXQ_QA_FRAGMENT_MAJOR) {
+        if (M <= 0 || N <= 0 || K <= 0 || !W) return MIXQ_E_SHAPE;
+        img = mixq::resolve_weight_image(W, N, K, static_cast<hipStream_t>(stream));
+        resolved = true;
+        const size_t need = gemm_scratch_bytes(M, N, K);
+        const mixq::GemmParams probe = plan_probe(M, N, K, O, 1, scratch && need && scratch_bytes >= need ? scratch : nullptr, img);
+        if (!mixq::gemm_takes_skinny(probe, mixq::EPI_DEQUANT)) return MIXQ_E_SHAPE; // (the image has ONE reader)
+    }
+    return gemm_mixed_impl(qA, W, sA, sW, fpA, fpW, Out, M, N, K, O, scratch, scratch_bytes, stream, qa_layout, img, resolved, bias, bf16);
 }
 
 int mixq_mixlinear_forward(int M, int N, int K, int O, void* x, const int32_t* ind, const int8_t* q_weight,

@@ -231,7 +231,10 @@ hipError_t launch_rmsnorm_quant(const void* X, const void* gamma, void* out, voi
                                 int q_layout = 0 /* 1: fragment-major int8 rows (quant == 8, quant_frag_layout_supported) */,
                                 // both or neither: the row is h = fp16(X + residual), written to h_out (may be X or residual, not out);
                                 // same form and grid as without, so the same bits as an fp16 add followed by the plain call
-                                const void* residual = nullptr, void* h_out = nullptr);
+                                const void* residual = nullptr, void* h_out = nullptr,
+                                // x, residual, h, gamma, out, the outliers and the scale are bf16 (quant 0 / 8): same form table, no clamp,
+                                // scale = bf16(amax / 127), q = sat(rint(out / scale)) -- launch_quant_extract's bf16 rules on the rounded row
+                                bool bf16 = false);
 hipError_t launch_find_outliers(const void* A, int M, int K, float sigma, unsigned* mask, int32_t* ind, int32_t* count,
                                 int capacity, hipStream_t st);
 hipError_t launch_dequant_columns(const int8_t* W, const void* sW, const int32_t* ind, int len, void* out, int N, int K,

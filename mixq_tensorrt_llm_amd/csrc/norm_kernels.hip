@@ -24,10 +24,14 @@ constexpr int NBLOCK = 256;
 // row from there on (sum of squares, normalisation, ... all see the rounded h), so every output has the bits of an fp16 add
 // followed by the ADD == false launch of the same form.  A lane holds its x and R vectors in registers before it stores h for
 // the same elements, and no lane reads another lane's: H may be X or R (not `out`).
+// BF (QUANT 0 / 8 only): x, R, H, gamma, out, the outliers and the scale are bf16.  h = bf16(x + R); out = bf16((row * rstd) * gamma)
+// without the clamp (bf16 has fp32's range: the +-64504 clamp is an fp16 overflow guard); scale = bf16(fp32(amax) / 127) and
+// q = sat[-127, 127](rint(out / scale)) on the ROUNDED bf16 row, one IEEE quotient per element -- quant_extract_kernel's BF rules
+// (quant_kernels.hip), so q and scale are what the bf16 quantiser makes of `out`.  Same TPR / MAXV / grid / reductions as the fp16 form.
 template <bool ADD> struct norm_row_ptr { typedef const uint16_t* __restrict__ type; };
 template <> struct norm_row_ptr<true> { typedef const uint16_t* type; }; // (H may alias it)
 
-template <int TPR, int MAXV, int QUANT, bool FRAG = false, bool ADD = false>
+template <int TPR, int MAXV, int QUANT, bool FRAG = false, bool ADD = false, bool BF = false>
 __global__ __launch_bounds__(NBLOCK) void rmsnorm_quant_kernel(typename norm_row_ptr<ADD>::type X,
                                                                const uint16_t* __restrict__ gamma,
                                                                uint16_t* __restrict__ out, uint16_t* __restrict__ outl,
@@ -35,6 +39,8 @@ __global__ __launch_bounds__(NBLOCK) void rmsnorm_quant_kernel(typename norm_row
                                                                uint16_t* __restrict__ scale, float eps, int M, int K,
                                                                int O, const uint16_t* R = nullptr, uint16_t* H = nullptr)
 {
+    static_assert(!(BF && QUANT == 4), "there is no bf16 int4 producer");
+    constexpr int INF_BITS = BF ? 0x7f80 : 0x7c00; // |x| bit pattern of +inf: larger patterns are NaNs
     constexpr int RPB = NBLOCK / TPR;
     __shared__ float redf[NBLOCK / 64];
     __shared__ int redi[NBLOCK / 64];
@@ -74,7 +80,7 @@ __global__ __launch_bounds__(NBLOCK) void rmsnorm_quant_kernel(typename norm_row
         }
         __syncthreads();
     }
-    if (ADD) { // h = fp16(x + R): stored once, and the row from here on
+    if (ADD) { // h = fp16(x + R) (BF: bf16(x + R)): stored once, and the row from here on
         uint4* hdst = reinterpret_cast<uint4*>(H + (row_ok ? row : 0) * (int64_t)K);
 #pragma unroll
         for (int v = 0; v < MAXV; ++v) {
@@ -84,8 +90,9 @@ __global__ __launch_bounds__(NBLOCK) void rmsnorm_quant_kernel(typename norm_row
             unsigned o[4];
 #pragma unroll
             for (int e = 0; e < 4; ++e)
-                o[e] = (unsigned)hadd_bits((uint16_t)(a[e] & 0xffffu), (uint16_t)(b[e] & 0xffffu)) |
-                       ((unsigned)hadd_bits((uint16_t)(a[e] >> 16), (uint16_t)(b[e] >> 16)) << 16);
+                if constexpr (BF) o[e] = __builtin_bit_cast(unsigned, bf2_add(__builtin_bit_cast(v2h, a[e]), b[e])); // (packed: one conversion per pair)
+                else o[e] = (unsigned)hadd_bits((uint16_t)(a[e] & 0xffffu), (uint16_t)(b[e] & 0xffffu)) |
+                            ((unsigned)hadd_bits((uint16_t)(a[e] >> 16), (uint16_t)(b[e] >> 16)) << 16);
             x[v] = make_uint4(o[0], o[1], o[2], o[3]);
             if (row_ok && idx < nvec) hdst[idx] = x[v];
         }
@@ -97,10 +104,15 @@ __global__ __launch_bounds__(NBLOCK) void rmsnorm_quant_kernel(typename norm_row
         const unsigned w[4] = {x[v].x, x[v].y, x[v].z, x[v].w};
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-            const float a = h2f((uint16_t)(w[e] & 0xffffu)), b = h2f((uint16_t)(w[e] >> 16));
+            const float a = o2f<BF>((uint16_t)(w[e] & 0xffffu)), b = o2f<BF>((uint16_t)(w[e] >> 16));
             ss = __builtin_fmaf(a, a, ss);
             ss = __builtin_fmaf(b, b, ss);
         }
+    }
+    if constexpr (BF) { // the row stays PACKED across the reduction: bf16 -> fp32 is a shift, and without this the compiler keeps the
+                        // widened copy of the whole row live for the normalisation (twice the registers, half the occupancy)
+#pragma unroll
+        for (int v = 0; v < MAXV; ++v) asm("" : "+v"(x[v].x), "+v"(x[v].y), "+v"(x[v].z), "+v"(x[v].w));
     }
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) ss += __shfl_xor(ss, off, 64);
@@ -123,11 +135,17 @@ __global__ __launch_bounds__(NBLOCK) void rmsnorm_quant_kernel(typename norm_row
             unsigned o[4];
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-                float a = (h2f((uint16_t)(w[e] & 0xffffu)) * rstd) * h2f((uint16_t)(gw[e] & 0xffffu));
-                float b = (h2f((uint16_t)(w[e] >> 16)) * rstd) * h2f((uint16_t)(gw[e] >> 16));
-                a = a > 0.f ? __builtin_fminf(a, 64504.f) : __builtin_fmaxf(a, -64504.f);
-                b = b > 0.f ? __builtin_fminf(b, 64504.f) : __builtin_fmaxf(b, -64504.f);
-                o[e] = (unsigned)f2h_bits_of_f32_result(a) | ((unsigned)f2h_bits_of_f32_result(b) << 16);
+                float a = (o2f<BF>((uint16_t)(w[e] & 0xffffu)) * rstd) * o2f<BF>((uint16_t)(gw[e] & 0xffffu));
+                float b = (o2f<BF>((uint16_t)(w[e] >> 16)) * rstd) * o2f<BF>((uint16_t)(gw[e] >> 16));
+                if (!BF) { // (fp16 overflow guard; bf16 has fp32's range)
+                    a = a > 0.f ? __builtin_fminf(a, 64504.f) : __builtin_fmaxf(a, -64504.f);
+                    b = b > 0.f ? __builtin_fminf(b, 64504.f) : __builtin_fmaxf(b, -64504.f);
+                }
+                // (plain norm: one packed conversion per pair keeps the store loop's registers at the fp16 form's; in front of the
+                //  quantiser the per-element form allocates fewer -- profiles/bf16_norm_resource_usage.txt)
+                if constexpr (BF && QUANT == 0) o[e] = __builtin_bit_cast(unsigned, f2bf2_of_f32_results(a, b));
+                else if constexpr (BF) o[e] = (unsigned)f2bf_bits(a) | ((unsigned)f2bf_bits(b) << 16);
+                else o[e] = (unsigned)f2h_bits_of_f32_result(a) | ((unsigned)f2h_bits_of_f32_result(b) << 16);
             }
             x[v] = make_uint4(o[0], o[1], o[2], o[3]);
             if (QUANT) reinterpret_cast<uint4*>(lrow)[idx] = x[v];
@@ -178,7 +196,7 @@ __global__ __launch_bounds__(NBLOCK) void rmsnorm_quant_kernel(typename norm_row
     };
     const int amax_all = row_max((int)max(m2 & 0xffffu, m2 >> 16));
     int amax = amax_all;
-    if (amax_all > 0x7c00) { // a NaN in the row: max with NaNs dropped (__hmax); -1 = every element is NaN
+    if (amax_all > INF_BITS) { // a NaN in the row: max with NaNs dropped (__hmax); -1 = every element is NaN
         amax = -1;
 #pragma unroll
         for (int v = 0; v < MAXV; ++v) {
@@ -187,8 +205,8 @@ __global__ __launch_bounds__(NBLOCK) void rmsnorm_quant_kernel(typename norm_row
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     int lo = (int)(w[e] & 0x7fffu), hi = (int)((w[e] >> 16) & 0x7fffu);
-                    lo = lo > 0x7c00 ? -1 : lo;
-                    hi = hi > 0x7c00 ? -1 : hi;
+                    lo = lo > INF_BITS ? -1 : lo;
+                    hi = hi > INF_BITS ? -1 : hi;
                     amax = max(amax, max(lo, hi));
                 }
             }
@@ -196,8 +214,8 @@ __global__ __launch_bounds__(NBLOCK) void rmsnorm_quant_kernel(typename norm_row
         amax = row_max(amax);
     }
     const uint16_t amax_bits = amax < 0 ? (uint16_t)0x7fffu : (uint16_t)amax;
-    const uint16_t s_bits = f2h_bits(h2f(amax_bits) / (QUANT == 4 ? 7.0f : 127.0f));
-    const float s = h2f(s_bits);
+    const uint16_t s_bits = BF ? f2bf_bits(bf2f(amax_bits) / 127.0f) : f2h_bits(h2f(amax_bits) / (QUANT == 4 ? 7.0f : 127.0f));
+    const float s = o2f<BF>(s_bits);
     const float rs = 1.0f / s;
     if (row_ok && t == 0) scale[row] = s_bits;
     if (QUANT == 4) { // packed int4 pairs: element 2i in the low nibble (cutlass::int4b_t), low 4 bits of half2int_rn
@@ -226,7 +244,25 @@ __global__ __launch_bounds__(NBLOCK) void rmsnorm_quant_kernel(typename norm_row
         return reinterpret_cast<uint2*>(q + (blk << 10) + (((idx >> 1) & 3) << 8) + ((r & 15) << 4) + ((idx & 1) << 3));
     };
     const bool stream_out = !FRAG && (int64_t)M * K >= ((int64_t)8 << 20); // prefill-size images: non-temporal stores (launch-uniform)
-    if (amax_all < 0x7c00 && s_bits != 0) { // every element finite, scale finite and non-zero (row-uniform)
+    if constexpr (BF) { // one IEEE quotient per element, every case (quant_extract_kernel's BF form)
+#pragma unroll
+        for (int v = 0; v < MAXV; ++v) {
+            const int idx = v * TPR + t;
+            if (row_ok && idx < nvec) {
+                typedef unsigned v2u_ __attribute__((ext_vector_type(2)));
+                const unsigned w[4] = {x[v].x, x[v].y, x[v].z, x[v].w};
+                unsigned o[2] = {0u, 0u};
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const int q0 = quant_one_bf16(bf2f((uint16_t)(w[e] & 0xffffu)), s);
+                    const int q1 = quant_one_bf16(bf2f((uint16_t)(w[e] >> 16)), s);
+                    o[e >> 1] |= (unsigned)(q0 | (q1 << 8)) << ((e & 1) * 16);
+                }
+                if (stream_out) __builtin_nontemporal_store(v2u_{o[0], o[1]}, reinterpret_cast<v2u_*>(slot(idx)));
+                else *slot(idx) = make_uint2(o[0], o[1]);
+            }
+        }
+    } else if (amax_all < 0x7c00 && s_bits != 0) { // every element finite, scale finite and non-zero (row-uniform)
 #pragma unroll
         for (int v = 0; v < MAXV; ++v) {
             const int idx = v * TPR + t;
@@ -256,22 +292,24 @@ __global__ __launch_bounds__(NBLOCK) void rmsnorm_quant_kernel(typename norm_row
 }
 
 // one name per instantiation and store form, built on its first launch (reporting only: mixq_debug_last_producer_kernel);
-// the ADD forms carry ",ADD=1" behind FRAG, the others keep the names they had
-static std::string norm_form_name(int tpr, int maxv, int quant, bool frag, bool add, bool nt)
+// the ADD forms carry ",ADD=1" behind FRAG, the others keep the names they had; a bf16 launch is the fp16 form's name + " [bf16]"
+// (the quantiser's convention), " nt" behind it
+static std::string norm_form_name(int tpr, int maxv, int quant, bool frag, bool add, bool bf, bool nt)
 {
     std::string n = producer_form_name("rmsnorm_quant_kernel", tpr, maxv, "QUANT", quant, frag, false);
     if (add) n.insert(n.size() - 1, ",ADD=1"); // "...,FRAG=0,ADD=1>"
-    return n + (nt ? " nt" : "");
+    return n + (bf ? " [bf16]" : "") + (nt ? " nt" : "");
 }
 
-template <int TPR, int MAXV, int QUANT, bool FRAG, bool ADD>
+template <int TPR, int MAXV, int QUANT, bool FRAG, bool ADD, bool BF>
 static void note_norm(bool nt)
 {
-    static const std::string n[2] = {norm_form_name(TPR, MAXV, QUANT, FRAG, ADD, false), norm_form_name(TPR, MAXV, QUANT, FRAG, ADD, true)};
+    static const std::string n[2] = {norm_form_name(TPR, MAXV, QUANT, FRAG, ADD, BF, false),
+                                     norm_form_name(TPR, MAXV, QUANT, FRAG, ADD, BF, true)};
     note_producer_kernel(n[nt ? 1 : 0].c_str());
 }
 
-template <int TPR, int MAXV, bool ADD>
+template <int TPR, int MAXV, bool ADD, bool BF>
 static hipError_t launch_norm(const uint16_t* X, const uint16_t* gamma, uint16_t* out, uint16_t* outl,
                               const int32_t* ind, int8_t* q, uint16_t* scale, float eps, int M, int K, int O,
                               int quant, hipStream_t st, int q_layout, const uint16_t* R, uint16_t* H)
@@ -280,10 +318,10 @@ static hipError_t launch_norm(const uint16_t* X, const uint16_t* gamma, uint16_t
         if (q_layout == 1 && quant == 8) {
             const size_t lds = (size_t)((K + 127) / 128) * 16 + (size_t)K * 2;
             static DeviceOnce oncef;
-            if (hipError_t e = ensure_dynamic_lds(rmsnorm_quant_kernel<TPR, MAXV, 8, true, ADD>, 160 * 1024 - 64, oncef); e != hipSuccess)
+            if (hipError_t e = ensure_dynamic_lds(rmsnorm_quant_kernel<TPR, MAXV, 8, true, ADD, BF>, 160 * 1024 - 64, oncef); e != hipSuccess)
                 return e;
-            note_norm<TPR, MAXV, 8, true, ADD>(false);
-            hipLaunchKernelGGL((rmsnorm_quant_kernel<TPR, MAXV, 8, true, ADD>), dim3((unsigned)M), dim3(NBLOCK), lds, st, X, gamma, out,
+            note_norm<TPR, MAXV, 8, true, ADD, BF>(false);
+            hipLaunchKernelGGL((rmsnorm_quant_kernel<TPR, MAXV, 8, true, ADD, BF>), dim3((unsigned)M), dim3(NBLOCK), lds, st, X, gamma, out,
                                outl, ind, q, scale, eps, M, K, O, R, H);
             return hipGetLastError();
         }
@@ -295,29 +333,37 @@ static hipError_t launch_norm(const uint16_t* X, const uint16_t* gamma, uint16_t
         const size_t lds = (size_t)((K + 127) / 128) * 16 + (size_t)RPB * K * 2;
         // rows of 8192 x 4 waves need more than the default 64 KiB of dynamic LDS
         static DeviceOnce once8, once4;
-        if (hipError_t e = ensure_dynamic_lds(rmsnorm_quant_kernel<TPR, MAXV, 8, false, ADD>, 160 * 1024 - 64, once8); e != hipSuccess)
+        if (hipError_t e = ensure_dynamic_lds(rmsnorm_quant_kernel<TPR, MAXV, 8, false, ADD, BF>, 160 * 1024 - 64, once8); e != hipSuccess)
             return e;
-        if (hipError_t e = ensure_dynamic_lds(rmsnorm_quant_kernel<TPR, MAXV, 4, false, ADD>, 160 * 1024 - 64, once4); e != hipSuccess)
-            return e;
-        if (quant == 4) note_norm<TPR, MAXV, 4, false, ADD>(false);
-        else note_norm<TPR, MAXV, 8, false, ADD>((int64_t)M * K >= ((int64_t)8 << 20)); // (the kernel's stream_out)
-        if (quant == 4)
-            hipLaunchKernelGGL((rmsnorm_quant_kernel<TPR, MAXV, 4, false, ADD>), grid, block, lds, st, X, gamma, out, outl, ind, q,
+        if constexpr (BF) { // (QUANT == 8 only)
+            if (quant != 8) return hipErrorInvalidValue;
+            note_norm<TPR, MAXV, 8, false, ADD, true>((int64_t)M * K >= ((int64_t)8 << 20));
+            hipLaunchKernelGGL((rmsnorm_quant_kernel<TPR, MAXV, 8, false, ADD, true>), grid, block, lds, st, X, gamma, out, outl, ind, q,
                                scale, eps, M, K, O, R, H);
-        else
-            hipLaunchKernelGGL((rmsnorm_quant_kernel<TPR, MAXV, 8, false, ADD>), grid, block, lds, st, X, gamma, out, outl, ind, q,
-                               scale, eps, M, K, O, R, H);
+            return hipGetLastError();
+        } else {
+            if (hipError_t e = ensure_dynamic_lds(rmsnorm_quant_kernel<TPR, MAXV, 4, false, ADD>, 160 * 1024 - 64, once4); e != hipSuccess)
+                return e;
+            if (quant == 4) note_norm<TPR, MAXV, 4, false, ADD, false>(false);
+            else note_norm<TPR, MAXV, 8, false, ADD, false>((int64_t)M * K >= ((int64_t)8 << 20)); // (the kernel's stream_out)
+            if (quant == 4)
+                hipLaunchKernelGGL((rmsnorm_quant_kernel<TPR, MAXV, 4, false, ADD>), grid, block, lds, st, X, gamma, out, outl, ind, q,
+                                   scale, eps, M, K, O, R, H);
+            else
+                hipLaunchKernelGGL((rmsnorm_quant_kernel<TPR, MAXV, 8, false, ADD>), grid, block, lds, st, X, gamma, out, outl, ind, q,
+                                   scale, eps, M, K, O, R, H);
+        }
     } else {
-        note_norm<TPR, MAXV, 0, false, ADD>(false);
-        hipLaunchKernelGGL((rmsnorm_quant_kernel<TPR, MAXV, 0, false, ADD>), grid, block, 0, st, X, gamma, out, outl, ind, q,
+        note_norm<TPR, MAXV, 0, false, ADD, BF>(false);
+        hipLaunchKernelGGL((rmsnorm_quant_kernel<TPR, MAXV, 0, false, ADD, BF>), grid, block, 0, st, X, gamma, out, outl, ind, q,
                            scale, eps, M, K, O, R, H);
     }
     return hipGetLastError();
 }
 
-// The form rules, once for both calls (ADD: with the residual add in front): the same (M, K, quant, q_layout) takes the same
-// TPR / MAXV / grid either way, so the reduction order -- and with it every bit -- is that of the unfused sequence.
-template <bool ADD>
+// The form rules, once for every call (ADD: with the residual add in front; BF: bf16 rows): the same (M, K, quant, q_layout) takes
+// the same TPR / MAXV / grid either way, so the reduction order -- and with it every bit -- is that of the unfused sequence.
+template <bool ADD, bool BF>
 static hipError_t launch_rmsnorm_form(const uint16_t* x, const uint16_t* g, uint16_t* o, uint16_t* ol, const int32_t* ind, int8_t* q,
                                       uint16_t* sc, float eps, int M, int K, int O, int quant, hipStream_t st, int q_layout,
                                       const uint16_t* r, uint16_t* h)
@@ -327,24 +373,26 @@ static hipError_t launch_rmsnorm_form(const uint16_t* x, const uint16_t* g, uint
     // a row is ONE load round trip of 1-4 vectors per lane instead of 8-16 on a single wavefront -- the same rule as the
     // quantiser's (quant_kernels.hip); 32 x 4096: 11.0 -> ~4.5 us for the fused producer (profiles/r03_small_m_timeline.txt)
     if ((M <= quant_block_rows(nvec, true) || q_layout == 1) && nvec > 64 * 2) { // (round 5: at every size here -- the table in quant_kernels.hip)
-        if (nvec <= 256 * 2) return launch_norm<256, 2, ADD>(x, g, o, ol, ind, q, sc, eps, M, K, O, quant, st, q_layout, r, h);
-        if (nvec <= 256 * 4) return launch_norm<256, 4, ADD>(x, g, o, ol, ind, q, sc, eps, M, K, O, quant, st, q_layout, r, h);
+        if (nvec <= 256 * 2) return launch_norm<256, 2, ADD, BF>(x, g, o, ol, ind, q, sc, eps, M, K, O, quant, st, q_layout, r, h);
+        if (nvec <= 256 * 4) return launch_norm<256, 4, ADD, BF>(x, g, o, ol, ind, q, sc, eps, M, K, O, quant, st, q_layout, r, h);
     }
-    if (nvec <= 64 * 2) return launch_norm<64, 2, ADD>(x, g, o, ol, ind, q, sc, eps, M, K, O, quant, st, 0, r, h);
-    if (nvec <= 64 * 4) return launch_norm<64, 4, ADD>(x, g, o, ol, ind, q, sc, eps, M, K, O, quant, st, 0, r, h);
-    if (nvec <= 64 * 8) return launch_norm<64, 8, ADD>(x, g, o, ol, ind, q, sc, eps, M, K, O, quant, st, 0, r, h);
-    if (nvec <= 64 * 16) return launch_norm<64, 16, ADD>(x, g, o, ol, ind, q, sc, eps, M, K, O, quant, st, 0, r, h);
-    if (nvec <= 256 * 8) return launch_norm<256, 8, ADD>(x, g, o, ol, ind, q, sc, eps, M, K, O, quant, st, q_layout, r, h);
-    if (nvec <= 256 * 16) return launch_norm<256, 16, ADD>(x, g, o, ol, ind, q, sc, eps, M, K, O, quant, st, 0, r, h);
+    if (nvec <= 64 * 2) return launch_norm<64, 2, ADD, BF>(x, g, o, ol, ind, q, sc, eps, M, K, O, quant, st, 0, r, h);
+    if (nvec <= 64 * 4) return launch_norm<64, 4, ADD, BF>(x, g, o, ol, ind, q, sc, eps, M, K, O, quant, st, 0, r, h);
+    if (nvec <= 64 * 8) return launch_norm<64, 8, ADD, BF>(x, g, o, ol, ind, q, sc, eps, M, K, O, quant, st, 0, r, h);
+    if (nvec <= 64 * 16) return launch_norm<64, 16, ADD, BF>(x, g, o, ol, ind, q, sc, eps, M, K, O, quant, st, 0, r, h);
+    if (nvec <= 256 * 8) return launch_norm<256, 8, ADD, BF>(x, g, o, ol, ind, q, sc, eps, M, K, O, quant, st, q_layout, r, h);
+    if (nvec <= 256 * 16) return launch_norm<256, 16, ADD, BF>(x, g, o, ol, ind, q, sc, eps, M, K, O, quant, st, 0, r, h);
     return hipErrorInvalidValue;
 }
 
 // quant = 0: plain RMSNorm (only `out`), 8 / 4: fused producer.  hipErrorInvalidValue for rows longer than 32768.
 // residual / h_out (both or neither): the row is h = fp16(X + residual), written to h_out (which may be X or residual).
+// bf16: every 16-bit operand is bf16 (quant 0 / 8 only).
 hipError_t launch_rmsnorm_quant(const void* X, const void* gamma, void* out, void* outl, const int32_t* ind, int8_t* q,
                                 void* scale, float eps, int M, int K, int O, int quant, hipStream_t st, int q_layout,
-                                const void* residual, void* h_out)
+                                const void* residual, void* h_out, bool bf16)
 {
+    if (bf16 && quant != 0 && quant != 8) return hipErrorInvalidValue;
     if (q_layout != 0 && !(q_layout == 1 && quant == 8 && quant_frag_layout_supported(M, K))) return hipErrorInvalidValue;
     if ((residual == nullptr) != (h_out == nullptr)) return hipErrorInvalidValue;
     if (M <= 0) return hipSuccess;
@@ -353,10 +401,13 @@ hipError_t launch_rmsnorm_quant(const void* X, const void* gamma, void* out, voi
     uint16_t* o = static_cast<uint16_t*>(out);
     uint16_t* ol = static_cast<uint16_t*>(outl);
     uint16_t* sc = static_cast<uint16_t*>(scale);
-    if (residual)
-        return launch_rmsnorm_form<true>(x, g, o, ol, ind, q, sc, eps, M, K, O, quant, st, q_layout,
-                                         static_cast<const uint16_t*>(residual), static_cast<uint16_t*>(h_out));
-    return launch_rmsnorm_form<false>(x, g, o, ol, ind, q, sc, eps, M, K, O, quant, st, q_layout, nullptr, nullptr);
+    const uint16_t* r = static_cast<const uint16_t*>(residual);
+    uint16_t* h = static_cast<uint16_t*>(h_out);
+    if (bf16)
+        return residual ? launch_rmsnorm_form<true, true>(x, g, o, ol, ind, q, sc, eps, M, K, O, quant, st, q_layout, r, h)
+                        : launch_rmsnorm_form<false, true>(x, g, o, ol, ind, q, sc, eps, M, K, O, quant, st, q_layout, nullptr, nullptr);
+    if (residual) return launch_rmsnorm_form<true, false>(x, g, o, ol, ind, q, sc, eps, M, K, O, quant, st, q_layout, r, h);
+    return launch_rmsnorm_form<false, false>(x, g, o, ol, ind, q, sc, eps, M, K, O, quant, st, q_layout, nullptr, nullptr);
 }
 
 } // namespace mixq

@@ -19,7 +19,7 @@ __all__ = ["FindRowScale", "ExtractOutliersAndSetToZeros", "int8FusedDequantize"
            "layernorm_forward_cuda_extract_outliers_int4", "ExtractOutliers", "dequantizeInt8Silu", "mixlinear_forward",
            "qa_layout", "qa_to_row_major", "QA_ROW_MAJOR", "QA_FRAGMENT_MAJOR", "WeightImage",
            "add_layernorm_forward_cuda", "add_layernorm_forward_cuda_extract_outliers",
-           "add_layernorm_forward_cuda_extract_outliers_int4"]
+           "add_layernorm_forward_cuda_extract_outliers_int4", "gemm_mixed"]
 
 QA_ROW_MAJOR, QA_FRAGMENT_MAJOR = 0, 1   # include/mixq.h MIXQ_QA_*
 
@@ -367,12 +367,41 @@ def FindRowScaleFusedExtracOutliers(x, scaleRow, ind, len_ind, rows, cols, q_lay
     return [q, outl]
 
 
+def _act_dtype(_input):
+    """The activation type a norm op runs in: bf16 for a bf16 ``_input`` (MI355X extension), else the reference's fp16."""
+    return torch.bfloat16 if _input.dtype == torch.bfloat16 else torch.float16
+
+
+def _act_name(dtype):
+    return "bf16" if dtype == torch.bfloat16 else "fp16"
+
+
+def _same_dtype(what, dtype, **operands):
+    """gamma, the outputs and the row scales of a norm op have ``_input``'s type: checked before anything reaches the library,
+    which sees raw pointers only."""
+    for name, t in operands.items():
+        if t is not None and t.dtype != dtype:
+            raise ValueError(f"{what}: {name} must be a {_act_name(dtype)} tensor like _input (got {t.dtype})")
+
+
+def _no_bf16_int4(what, _input):
+    if _input.dtype == torch.bfloat16:
+        raise TypeError(f"{what}: there is no bf16 form of the packed 4-bit producer (fp16 tensors only)")
+
+
 @_on_tensor_device
 def layernorm_forward_cuda(_input, _gamma, _out, eps):
-    """layernorm.cu:100-117: T5-style RMSNorm of _input [b, n, c] (or [m, c]) into _out."""
+    """layernorm.cu:100-117: T5-style RMSNorm of _input [b, n, c] (or [m, c]) into _out.
+    A bf16 ``_input`` (MI355X extension, ``mixq_rmsnorm_typed``) takes bf16 ``_gamma`` / ``_out``."""
+    dt = _act_dtype(_input)
+    _same_dtype("layernorm_forward_cuda", dt, _input=_input, _gamma=_gamma, _out=_out)
     _dev(_input, _gamma, _out)
     c = _input.shape[-1]
     m = _input.numel() // c
+    if dt == torch.bfloat16:
+        _lib.check(_lib.load().mixq_rmsnorm_typed(m, c, _p(_input), None, None, _p(_gamma), _p(_out), ctypes.c_float(eps),
+                                                  _lib.MIXQ_TYPE_BF16, _st(_input)), "layernorm_forward_cuda")
+        return
     _lib.check(_lib.load().mixq_rmsnorm(m, c, _p(_input), _p(_gamma), _p(_out), ctypes.c_float(eps), _st(_input)),
                "layernorm_forward_cuda")
 
@@ -381,14 +410,24 @@ def layernorm_forward_cuda(_input, _gamma, _out, eps):
 def layernorm_forward_cuda_extract_outliers(_input, _gamma, _out, eps, _ind, scaleRow, q_layout=0):
     """layernorm.cu:316-346: fused RMSNorm -> extract(+zero) outliers -> per-row int8 quantisation.
     Fills _out (normalised, outlier columns zeroed) and scaleRow; returns [outliers fp16 [m,len], quant int8 [m,c]].
-    ``q_layout`` (MI355X extension): write the int8 rows in the consumer's preferred image (``qa_layout()``)."""
+    ``q_layout`` (MI355X extension): write the int8 rows in the consumer's preferred image (``qa_layout()``).
+    A bf16 ``_input`` (MI355X extension, ``mixq_rmsnorm_extract_quant_typed``) takes bf16 ``_gamma`` / ``_out`` / ``scaleRow`` and
+    returns bf16 outliers; the int8 rows follow the bf16 quantiser's rules (scale = bf16(amax / 127), no fp16 quotient)."""
+    dt = _act_dtype(_input)
+    _same_dtype("layernorm_forward_cuda_extract_outliers", dt, _input=_input, _gamma=_gamma, _out=_out, scaleRow=scaleRow)
     _dev(_input, _gamma, _out, _ind, scaleRow)
     c = _input.shape[-1]
     m = _input.numel() // c
     _rows_fit(scaleRow, m, "layernorm_forward_cuda_extract_outliers")
     n = _ind.shape[0]
-    outl = torch.zeros((m, n), dtype=torch.float16, device=_input.device)
+    outl = torch.zeros((m, n), dtype=dt, device=_input.device)
     q = _alloc_q(m, c, q_layout, _input.device)
+    if dt == torch.bfloat16:
+        _lib.check(_lib.load().mixq_rmsnorm_extract_quant_typed(m, c, _p(_input), None, None, _p(_gamma), _p(_out), ctypes.c_float(eps),
+                                                                _p(_ind), n, _p(outl), _p(q), _p(scaleRow), q_layout,
+                                                                _lib.MIXQ_TYPE_BF16, _st(_input)),
+                   "layernorm_forward_cuda_extract_outliers")
+        return [outl, q]
     _lib.check(_lib.load().mixq_rmsnorm_extract_quant_layout(m, c, _p(_input), _p(_gamma), _p(_out), ctypes.c_float(eps),
                                                              _p(_ind), n, _p(outl), _p(q), _p(scaleRow), q_layout,
                                                              _st(_input)),
@@ -399,7 +438,8 @@ def layernorm_forward_cuda_extract_outliers(_input, _gamma, _out, eps, _ind, sca
 @_on_tensor_device
 def layernorm_forward_cuda_extract_outliers_int4(_input, _gamma, _out, eps, _ind, scaleRow):
     """layernorm.cu:379-414: the same fused producer with packed 4-bit rows (scale = amax / 7).
-    Returns [outliers fp16 [m,len], quant uint8 [m, c/2]]."""
+    Returns [outliers fp16 [m,len], quant uint8 [m, c/2]].  fp16 only: a bf16 ``_input`` raises ``TypeError``."""
+    _no_bf16_int4("layernorm_forward_cuda_extract_outliers_int4", _input)
     _dev(_input, _gamma, _out, _ind, scaleRow)
     c = _input.shape[-1]
     m = _input.numel() // c
@@ -414,11 +454,13 @@ def layernorm_forward_cuda_extract_outliers_int4(_input, _gamma, _out, eps, _ind
 
 
 def _add_operands(_input, _residual, h_out, what):
-    """The residual-add forms' row operands: same shape, fp16, contiguous; ``h_out`` None = in place into ``_residual``."""
+    """The residual-add forms' row operands: same shape, ``_input``'s type (fp16, or bf16 for a bf16 ``_input``), contiguous;
+    ``h_out`` None = in place into ``_residual``."""
     h = _residual if h_out is None else h_out
+    dt = _act_dtype(_input)
     for name, t in (("_input", _input), ("_residual", _residual), ("h_out", h)):
-        if t.dtype != torch.float16 or not t.is_contiguous():
-            raise ValueError(f"{what}: {name} must be a contiguous fp16 tensor (got {t.dtype}, contiguous={t.is_contiguous()})")
+        if t.dtype != dt or not t.is_contiguous():
+            raise ValueError(f"{what}: {name} must be a contiguous {_act_name(dt)} tensor (got {t.dtype}, contiguous={t.is_contiguous()})")
         if t.shape != _input.shape:
             raise ValueError(f"{what}: {name} has shape {tuple(t.shape)}, _input has {tuple(_input.shape)}")
     return h
@@ -430,9 +472,15 @@ def add_layernorm_forward_cuda(_input, _residual, _gamma, _out, eps, h_out=None)
     pass; h goes to ``h_out`` (None: in place into ``_residual``; it may also be ``_input``) and is returned.  Same bits as the
     torch add followed by ``layernorm_forward_cuda``."""
     h = _add_operands(_input, _residual, h_out, "add_layernorm_forward_cuda")
+    dt = _act_dtype(_input)
+    _same_dtype("add_layernorm_forward_cuda", dt, _gamma=_gamma, _out=_out)
     _dev(_input, _residual, h, _gamma, _out)
     c = _input.shape[-1]
     m = _input.numel() // c
+    if dt == torch.bfloat16:   # (``mixq_rmsnorm_typed``: h = bf16(_input + _residual), torch's bf16 add)
+        _lib.check(_lib.load().mixq_rmsnorm_typed(m, c, _p(_input), _p(_residual), _p(h), _p(_gamma), _p(_out), ctypes.c_float(eps),
+                                                  _lib.MIXQ_TYPE_BF16, _st(_input)), "add_layernorm_forward_cuda")
+        return h
     _lib.check(_lib.load().mixq_add_rmsnorm(m, c, _p(_input), _p(_residual), _p(h), _p(_gamma), _p(_out), ctypes.c_float(eps),
                                             _st(_input)), "add_layernorm_forward_cuda")
     return h
@@ -443,13 +491,21 @@ def add_layernorm_forward_cuda_extract_outliers(_input, _residual, _gamma, _out,
     """MI355X extension (``mixq_add_rmsnorm_extract_quant_layout``): ``layernorm_forward_cuda_extract_outliers`` on
     h = _input + _residual in one pass; h goes to ``h_out`` (None: in place into ``_residual``).  Returns [outliers, quant]."""
     h = _add_operands(_input, _residual, h_out, "add_layernorm_forward_cuda_extract_outliers")
+    dt = _act_dtype(_input)
+    _same_dtype("add_layernorm_forward_cuda_extract_outliers", dt, _gamma=_gamma, _out=_out, scaleRow=scaleRow)
     _dev(_input, _residual, h, _gamma, _out, _ind, scaleRow)
     c = _input.shape[-1]
     m = _input.numel() // c
     _rows_fit(scaleRow, m, "add_layernorm_forward_cuda_extract_outliers")
     n = _ind.shape[0]
-    outl = torch.zeros((m, n), dtype=torch.float16, device=_input.device)
+    outl = torch.zeros((m, n), dtype=dt, device=_input.device)
     q = _alloc_q(m, c, q_layout, _input.device)
+    if dt == torch.bfloat16:   # (``mixq_rmsnorm_extract_quant_typed``)
+        _lib.check(_lib.load().mixq_rmsnorm_extract_quant_typed(m, c, _p(_input), _p(_residual), _p(h), _p(_gamma), _p(_out),
+                                                                ctypes.c_float(eps), _p(_ind), n, _p(outl), _p(q), _p(scaleRow), q_layout,
+                                                                _lib.MIXQ_TYPE_BF16, _st(_input)),
+                   "add_layernorm_forward_cuda_extract_outliers")
+        return [outl, q]
     _lib.check(_lib.load().mixq_add_rmsnorm_extract_quant_layout(m, c, _p(_input), _p(_residual), _p(h), _p(_gamma), _p(_out),
                                                                  ctypes.c_float(eps), _p(_ind), n, _p(outl), _p(q), _p(scaleRow),
                                                                  q_layout, _st(_input)),
@@ -460,7 +516,8 @@ def add_layernorm_forward_cuda_extract_outliers(_input, _residual, _gamma, _out,
 @_on_tensor_device
 def add_layernorm_forward_cuda_extract_outliers_int4(_input, _residual, _gamma, _out, eps, _ind, scaleRow, h_out=None):
     """MI355X extension (``mixq_add_rmsnorm_extract_quant4``): the same with packed 4-bit rows (scale = amax / 7).
-    Returns [outliers fp16 [m,len], quant uint8 [m, c/2]]."""
+    Returns [outliers fp16 [m,len], quant uint8 [m, c/2]].  fp16 only: a bf16 ``_input`` raises ``TypeError``."""
+    _no_bf16_int4("add_layernorm_forward_cuda_extract_outliers_int4", _input)
     h = _add_operands(_input, _residual, h_out, "add_layernorm_forward_cuda_extract_outliers_int4")
     _dev(_input, _residual, h, _gamma, _out, _ind, scaleRow)
     c = _input.shape[-1]
@@ -559,6 +616,35 @@ def mixq_linear(A, W_int8, sW, fp_weight, ind, out=None, workspace=None):
     scr = gemm_scratch(A, M, N, K)
     _lib.check(lib.mixq_gemm_mixed_scratch(_p(qA), _p(W_int8), _p(sA), _p(sW), _p(fpA), _p(fp_weight), _p(out), M, N, K, O,
                                            _p(scr), scr.numel() if scr is not None else 0, _st(A)), "gemm_mixed")
+    return out
+
+
+@_on_tensor_device
+def gemm_mixed(q, W_int8, x_scale, sW, outliers, fp_weight, M, N, K, bias=None, qa_layout=0, out=None):
+    """MI355X extension (``mixq_gemm_mixed_typed``): the fused GEMM on a producer's output -- ``q`` int8 rows (or the
+    fragment-major image, ``qa_layout``), ``x_scale`` [M], ``outliers`` [M, O] as ``layernorm_forward_cuda_extract_outliers``
+    leaves them -- with W int8 [N, K], ``sW`` fp16 [N], ``fp_weight`` [N, O] and an optional ``bias`` [N] added in the epilogue.
+    fp16 or bf16: the type is ``outliers``' (``x_scale``'s when there are no outlier columns); ``x_scale``, ``fp_weight``, ``bias``
+    and ``out`` must have it, ``sW`` stays fp16.  Returns ``out`` [M, N] (allocated unless given)."""
+    O = 0 if outliers is None else int(outliers.shape[-1])
+    dt = outliers.dtype if O else x_scale.dtype
+    if dt not in (torch.float16, torch.bfloat16):
+        raise TypeError(f"gemm_mixed: the activation type is {dt}; fp16 and bf16 are supported")
+    for name, t in (("x_scale", x_scale), ("fp_weight", fp_weight if O else None), ("bias", bias), ("out", out)):
+        if t is not None and t.dtype != dt:
+            raise TypeError(f"gemm_mixed: {name} is {t.dtype} in a {_act_name(dt)} call (x_scale, outliers, fp_weight, bias and out share one type)")
+    if sW.dtype != torch.float16 or q.dtype != torch.int8 or W_int8.dtype != torch.int8:
+        raise TypeError("gemm_mixed: q and W_int8 are int8, sW is fp16")
+    _dev(*(t for t in (q, W_int8, x_scale, sW, outliers if O else None, fp_weight if O else None, bias, out) if t is not None))
+    _rows_fit(x_scale, M, "gemm_mixed")
+    if out is None:
+        out = torch.empty((M, N), dtype=dt, device=q.device)
+    assert out.numel() == M * N and (bias is None or bias.numel() == N) and sW.numel() >= N
+    scr = None if qa_layout else gemm_scratch(q, M, N, K)
+    _lib.check(_lib.load().mixq_gemm_mixed_typed(_p(q), _p(W_int8), _p(x_scale), _p(sW), _p(outliers) if O else None,
+                                                 _p(fp_weight) if O else None, _p(bias), _p(out), M, N, K, O, qa_layout,
+                                                 _lib.MIXQ_TYPE_BF16 if dt == torch.bfloat16 else _lib.MIXQ_TYPE_HALF, _p(scr),
+                                                 scr.numel() if scr is not None else 0, _st(q)), "gemm_mixed")
     return out
 
 

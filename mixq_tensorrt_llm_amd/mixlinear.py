@@ -71,11 +71,14 @@ def outlier_product(activation_outliers: torch.Tensor, weight_cache: torch.Tenso
 
 
 class MixLibCache:
-    """Cache.py:5-24: per-model scratch shared by the layers (row scales, sigma, the running outlier state)."""
+    """Cache.py:5-24: per-model scratch shared by the layers (row scales, sigma, the running outlier state).
+    ``dtype=torch.bfloat16`` (MI355X extension): the row scales of a bf16 producer (``FasterTransformerRMSNorm(dtype=bf16)``)."""
 
-    def __init__(self, inputdim=1024, sigma=6, bit=8, device="cuda"):
+    def __init__(self, inputdim=1024, sigma=6, bit=8, device="cuda", dtype=torch.float16):
+        assert dtype in (torch.float16, torch.bfloat16)
         self.device = device
-        self.x_scale = torch.zeros((inputdim, 1), dtype=torch.float16, device=device)
+        self.dtype = dtype
+        self.x_scale = torch.zeros((inputdim, 1), dtype=dtype, device=device)
         self.sigma = torch.zeros((1, 1), dtype=torch.float16, device=device)
         self.sigma[0] = sigma
         self.zeros = None  # (the reference keeps an [inputdim, 36864] zero matrix as the "no outliers" addend; a null
@@ -345,10 +348,16 @@ class MixLinear_GEMM:
 class FasterTransformerRMSNorm:
     """MixQ/src/mixquant/modules/fused/norm.py:6-40: RMSNorm that, when ``next_layer`` is a MixLinear_GEMM, also
     extracts (+zeroes) that layer's outlier columns and quantises the rows in the same pass over the hidden state
-    (`mixq_rmsnorm_extract_quant`), leaving q_xcache / x_scale / activation_outliers in the cache."""
+    (`mixq_rmsnorm_extract_quant`), leaving q_xcache / x_scale / activation_outliers in the cache.
 
-    def __init__(self, weight, eps=1e-6, cache=None):
-        self.weight = weight.to(torch.float16)
+    ``dtype=torch.bfloat16`` (MI355X extension): a bf16 norm -- bf16 hidden state, gamma, outliers and row scales (the cache's
+    ``x_scale`` must be bf16: ``MixLibCache(dtype=torch.bfloat16)``) -- in front of a layer with ``bit == 8`` that consumes the
+    cache in bf16 (``plugin.MixQLinear(dtype=torch.bfloat16).forward_quantised``).  There is no bf16 4-bit producer."""
+
+    def __init__(self, weight, eps=1e-6, cache=None, dtype=torch.float16):
+        assert dtype in (torch.float16, torch.bfloat16)
+        self.dtype = dtype
+        self.weight = weight.to(dtype)
         self.variance_epsilon = eps
         self.cache = cache
         self.next_layer = None
@@ -378,6 +387,8 @@ class FasterTransformerRMSNorm:
                 self.cache.activation_outliers, self.cache.q_xcache = mixlib.layernorm_forward_cuda_extract_outliers(
                     x, self.weight, output, self.variance_epsilon, self.next_layer.ind, self.cache.x_scale, lay)
         elif self.next_layer.bit == 4:
+            if self.dtype == torch.bfloat16:
+                raise TypeError("FasterTransformerRMSNorm: there is no bf16 form of the 4-bit producer (next_layer.bit == 4)")
             if add:
                 self.cache.activation_outliers, self.cache.q_xcache = mixlib.add_layernorm_forward_cuda_extract_outliers_int4(
                     x, residual, self.weight, output, self.variance_epsilon, self.next_layer.ind, self.cache.x_scale)

@@ -291,4 +291,34 @@ class MixQLinear:
                 x = all_gather_columns(x, self.tp_group, self.tp_size)
         return x
 
+    # ---- as the ``next_layer`` of a fused norm (mixlinear.FasterTransformerRMSNorm): a static set of 128 outlier columns, 8 bits ----
+    bit = 8
+    add_outliers = False
+
+    @property
+    def ind(self) -> torch.Tensor:
+        """The outlier columns as the producers take them: the int32 [128] view of ``fp_ind``."""
+        return self.fp_ind.view(torch.int32)
+
+    def forward_quantised(self, q, x_scale, outliers, q_layout: int = 0, lead_shape=None) -> torch.Tensor:
+        """MI355X extension: this layer's GEMM on what a fused norm producer has already written -- int8 rows ``q`` (row-major, or the
+        fragment-major image with ``q_layout``), row scales ``x_scale`` and ``outliers`` [M, 128], in the layer's dtype -- through
+        ``mixlib.gemm_mixed`` (``mixq_gemm_mixed_typed``) with the bias in the epilogue.  No quantiser pass and no second read of the
+        normalised row.  A bf16 block:
+
+            n, h = norm.forward_residual(x, residual)
+            y = linear.forward_quantised(cache.q_xcache, cache.x_scale, cache.activation_outliers, cache.q_layout)
+
+        ``lead_shape``: the leading dimensions of the result (default: [M])."""
+        from . import mixlib
+        if self.tp_size > 1:
+            raise ValueError("MixQLinear.forward_quantised: a row-sharded layer (tp_size > 1) has no producer-fed path")
+        if outliers.dtype != self.dtype or x_scale.dtype != self.dtype:
+            raise TypeError(f"MixQLinear.forward_quantised: a {self.dtype} layer got {outliers.dtype} outliers and {x_scale.dtype} row scales")
+        M = outliers.shape[0]
+        bias = None if self.bias is None else fp16_bias(self.bias, self.out_features, outliers.device, self.dtype)
+        y = mixlib.gemm_mixed(q, self.weight.view(torch.int8), x_scale, self.weights_scaling_factor, outliers, self.fp_weight, M,
+                              self.out_features, self.in_features, bias=bias, qa_layout=q_layout)
+        return y if lead_shape is None else y.reshape(*lead_shape, self.out_features)
+
     __call__ = forward
