@@ -345,6 +345,23 @@ MIXQ_API int mixq_gemm_mixed_layout(const int8_t* qA, const int8_t* W, const voi
 MIXQ_API int mixq_gemm_mixed_typed(const int8_t* qA, const int8_t* W, const void* sA, const void* sW, const void* fpA, const void* fpW,
                                    const void* bias, void* Out, int M, int N, int K, int O, int qa_layout, int type, void* scratch,
                                    size_t scratch_bytes, void* stream);
+/* mixq_gemm_mixed_typed with an activation in the epilogue of the same launch (MI355X extension): the gate projection of an MLP, outlier
+ * product included, as ONE launch in either type.  `epilogue` uses the numbering of mixq_int8_fused_dequantize_layout: 0 plain -- exactly
+ * mixq_gemm_mixed_typed with a NULL bias, bit for bit --, 1 SiLU, 3 SiLU x mul.  Per element, T the call's type, P the in-kernel outlier
+ * product rounded to T:
+ *     v   = fma(float(acc), float(sW[n]) * float(sA[m]), float(P))      fp32
+ *     g   = T_rn(v / (1 + expf(-v)))                                    fp32 SiLU, IEEE division, one rounding
+ *     Out = g                                                           (1)
+ *     Out = T_rn(float(g) * float(mul[m, n]))                           (3) one multiply of the ROUNDED g; mul is [M, N] of type T
+ * The kernel is the one mixq_gemm_mixed_typed launches for the shape (mixq_debug_last_gemm_kernel reports the same name).  Checks, in this
+ * order: MIXQ_E_TYPE (type is neither MIXQ_TYPE_HALF nor MIXQ_TYPE_BF16); MIXQ_E_BADARG (epilogue not 0 / 1 / 3, mul NULL with 3 or
+ * non-NULL otherwise, Out == mul, a null operand, a negative size, a bad qa_layout); MIXQ_E_SHAPE (O > 128 with a non-zero epilogue or
+ * bf16, fragment-major where the skinny kernel does not serve the shape, K % 16, N % 16, O % 8); MIXQ_E_ALIGN (mul 16-byte aligned like
+ * Out, the rest as the typed entry).  M == 0 or N == 0 returns MIXQ_OK without touching the device.  No bias.  Asynchronous, no
+ * allocation, capturable; scratch as mixq_gemm_mixed_scratch (may be NULL); every buffer is used at exactly its declared size. */
+MIXQ_API int mixq_gemm_mixed_act_typed(const int8_t* qA, const int8_t* W, const void* sA, const void* sW, const void* fpA, const void* fpW,
+                                       const void* mul, void* Out, int M, int N, int K, int O, int epilogue, int qa_layout, int type,
+                                       void* scratch, size_t scratch_bytes, void* stream);
 /* MixLinear_GEMM.forward (MixQ/src/mixquant/modules/linear.py:163-286, bit = 8, static outlier set) as ONE call and TWO
  * launches: the reference makes four mixlib calls per linear here (ExtractOutliersAndSetToZeros, FindRowScale, torch.mm on the
  * outliers, int8FusedDequantize); a decode step is host-bound on those calls long before it is GPU-bound
@@ -614,7 +631,7 @@ MIXQ_API const char* mixq_version(void);
  * header can refuse to run instead of passing shifted arguments: `if (mixq_abi_version() != MIXQ_ABI_VERSION) fail`.  The
  * reference-named entries (initOpenAiTritonPlugins, the plugin lifecycle, mixq_enqueue) have not changed since revision 1.
  * Revision 5 adds entries only (mixq_enqueue_bias, mixq_enqueue_tp_bias, mixq_gemm_mixed_bias; later, still 5: mixq_add_rmsnorm*,
- * mixq_rmsnorm_typed, mixq_rmsnorm_extract_quant_typed, mixq_gemm_mixed_typed). */
+ * mixq_rmsnorm_typed, mixq_rmsnorm_extract_quant_typed, mixq_gemm_mixed_typed, mixq_gemm_mixed_act_typed). */
 #define MIXQ_ABI_VERSION 5
 MIXQ_API int mixq_abi_version(void);
 MIXQ_API const char* mixq_error_string(int code);

@@ -113,6 +113,7 @@ __device__ __forceinline__ void mid_finish(const GemmParams& p, char* smem, v16i
     const int lr = lane & 31, lh = lane >> 5;
     const bool has_outliers = p.O > 0;
     dbg_stamp(p.dbg, 3); // last MFMA issued (this wave)
+    constexpr bool HAS_MUL = epi_has_mul(EPI);
     uint2 mulq[KEEP][2]; // (the multiplicand of gate * up: requested here, in front of the exchange)
 #pragma unroll
     for (int k = 0; k < KEEP; ++k) {
@@ -120,7 +121,7 @@ __device__ __forceinline__ void mid_finish(const GemmParams& p, char* smem, v16i
 #pragma unroll
         for (int g2 = 0; g2 < 2; ++g2) {
             const int64_t at = (int64_t)min(t.m(m0, wm, lr), p.M - 1) * p.N + min(t.n(n0, wn, lh) + 8 * g2, p.N - 4);
-            mulq[k][g2] = EPI == EPI_DEQUANT_SILU_MUL ? *reinterpret_cast<const uint2*>(p.Mul + at) : make_uint2(0u, 0u);
+            mulq[k][g2] = HAS_MUL ? *reinterpret_cast<const uint2*>(p.Mul + at) : make_uint2(0u, 0u);
         }
     }
     __syncthreads(); // B0
@@ -267,12 +268,12 @@ __device__ __forceinline__ void mid_finish(const GemmParams& p, char* smem, v16i
                         if (epi_has_silu(EPI)) v = silu_f32(v);
                         oh[e] = f2o_bits_of_f32_result<epi_bf16(EPI)>(v);
                     }
-                    if (EPI == EPI_DEQUANT_SILU_MUL) { // gate * up: one fp16 multiply of the rounded result
+                    if (HAS_MUL) { // gate * up: one fp16 (bf16) multiply of the rounded result
                         const uint2 mb = mulq[k][g2];
                         const uint16_t mh[4] = {(uint16_t)(mb.x & 0xffffu), (uint16_t)(mb.x >> 16), (uint16_t)(mb.y & 0xffffu),
                                                 (uint16_t)(mb.y >> 16)};
 #pragma unroll
-                        for (int e = 0; e < 4; ++e) oh[e] = f2h_bits(h2f(oh[e]) * h2f(mh[e]));
+                        for (int e = 0; e < 4; ++e) oh[e] = omul_bits<epi_bf16(EPI)>(oh[e], mh[e]);
                     }
                     if constexpr (epi_bias(EPI)) { // the layer's bias: one fp16 (bf16) add of the rounded result
                         const uint2 bb = pre.bias[k][g2];

@@ -324,7 +324,7 @@ __global__ __launch_bounds__(512) void gemm_w8a8o16_pp128_kernel(const GemmParam
             for (int g = 0; g < 4; ++g)
                 bq[i][g] = *reinterpret_cast<const uint2*>(p.bias + min(n0 + wn * 64 + i * 32 + 4 * lh + 8 * g, p.N - 4));
     }
-    constexpr bool HAS_MUL = EPI == EPI_DEQUANT_SILU_MUL;
+    constexpr bool HAS_MUL = epi_has_mul(EPI);
     uint2 yq[2][4], mq[2][4];
     uint4 ypre[4], mpre[4];
 #pragma unroll
@@ -398,7 +398,7 @@ __global__ __launch_bounds__(512) void gemm_w8a8o16_pp128_kernel(const GemmParam
                     v1 = silu_f32(v1);
                 }
                 v2h o16 = f2o2_of_f32_results<epi_bf16(EPI)>(v0, v1);
-                if (EPI == EPI_DEQUANT_SILU_MUL) o16 = o16 * __builtin_bit_cast(v2h, e2 ? mulq.y : mulq.x); // gate * up
+                if (epi_has_mul(EPI)) o16 = omul2<epi_bf16(EPI)>(o16, e2 ? mulq.y : mulq.x); // gate * up
                 if constexpr (EPI == EPI_DEQUANT_BIAS) o16 = o16 + __builtin_bit_cast(v2h, e2 ? bq[i][g].y : bq[i][g].x); // + bias (fp16 add)
                 if constexpr (EPI == EPI_DEQUANT_BIAS_BF16) o16 = bf2_add(o16, e2 ? bq[i][g].y : bq[i][g].x); // + bias (bf16 add)
                 __builtin_memcpy(&ow[e2 >> 1], &o16, 4);

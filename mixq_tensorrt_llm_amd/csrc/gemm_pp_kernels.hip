@@ -615,7 +615,13 @@ __global__ __launch_bounds__(512) void gemm_w8a8o16_pp_kernel(const GemmParams p
     // reverse: coalesced 16-byte loads of 128-byte row segments (8 rows per instruction), one block ahead, then through
     // the wave's window into the accumulator layout (8 bytes = 4 consecutive n of row lane & 31).  Reading them in the
     // accumulator layout directly costs 32 cache lines of 16 useful bytes per load instruction.
-    constexpr bool HAS_MUL = EPI == EPI_DEQUANT_SILU_MUL;
+    // (bf16 SiLU x up) the multiplicand is NOT carried through dequant like that: mq + mpre are 32 more registers next to the widening and
+    // rounding of the bf16 build, which spilled.  The rows are multiplied as they leave the window instead: flush requests the multiplicand
+    // in the layout it stores in (the same 16-byte pieces of 128-byte row segments), late, from an address the compiler cannot hoist.
+    constexpr bool MUL_LATE = epi_has_mul(EPI) && BF;
+    constexpr bool HAS_MUL = epi_has_mul(EPI) && !MUL_LATE;
+    // (bf16 SiLU builds) the next tile's outlier product is issued behind this tile's dequant, not under it: 16 registers less across the SiLU
+    constexpr bool P_BEHIND = epi_has_silu(EPI) && BF;
     uint2 yq[2][4], mq[2][4];
     uint4 ypre[4], mpre[4];
 #pragma unroll
@@ -699,7 +705,7 @@ __global__ __launch_bounds__(512) void gemm_w8a8o16_pp_kernel(const GemmParams p
                     v1 = silu_f32(v1);
                 }
                 v2h o16 = f2o2_of_f32_results<BF>(v0, v1);
-                if (EPI == EPI_DEQUANT_SILU_MUL) o16 = o16 * __builtin_bit_cast(v2h, e2 ? mulq.y : mulq.x); // gate * up
+                if (HAS_MUL) o16 = omul2<BF>(o16, e2 ? mulq.y : mulq.x); // gate * up
                 if constexpr (EPI == EPI_DEQUANT_BIAS) o16 = o16 + __builtin_bit_cast(v2h, e2 ? bq[g].y : bq[g].x); // + bias (fp16 add)
                 if constexpr (EPI == EPI_DEQUANT_BIAS_BF16) o16 = bf2_add(o16, e2 ? bq[g].y : bq[g].x); // + bias (bf16 add)
                 __builtin_memcpy(&ow[e2 >> 1], &o16, 4);
@@ -707,8 +713,14 @@ __global__ __launch_bounds__(512) void gemm_w8a8o16_pp_kernel(const GemmParams p
             if (S == 8) { // a single 32x32 tile per wave: 8-byte stores straight from the accumulator layout
                 const int m = m0 + wm * 128 + jmap(j) * 32 + lr;
                 const int n = n0 + wn * 64 + imap(i) * 32 + 4 * lh + 8 * g;
-                if (m < p.M && n < p.N)
+                if (m < p.M && n < p.N) {
+                    if constexpr (MUL_LATE) { // gate * up, straight from the accumulator layout (one tile per wave)
+                        const uint2 mb = *reinterpret_cast<const uint2*>(p.Mul + (int64_t)m * p.N + n);
+                        ow[0] = __builtin_bit_cast(unsigned, omul2<true>(__builtin_bit_cast(v2h, ow[0]), mb.x));
+                        ow[1] = __builtin_bit_cast(unsigned, omul2<true>(__builtin_bit_cast(v2h, ow[1]), mb.y));
+                    }
                     *reinterpret_cast<uint2*>(static_cast<uint16_t*>(p.D) + (int64_t)m * p.N + n) = uint2{ow[0], ow[1]};
+                }
                 continue;
             }
             const int c = i * 4 + g; // 16-byte chunk of the 128-byte row
@@ -732,6 +744,17 @@ __global__ __launch_bounds__(512) void gemm_w8a8o16_pp_kernel(const GemmParams p
         const int rd = (int)((ln >> 3) * 128 + (((ln & 7) ^ (ln >> 3)) << 4));
         const unsigned dlane = ((ln >> 3) * (unsigned)p.N + (ln & 7) * 8) * 2;
         uint4 v[4];
+        uint4 mv[4]; // (MUL_LATE) the multiplicand of these rows
+        (void)mv;
+        if constexpr (MUL_LATE) {
+            const char* const mwave = reinterpret_cast<const char*>(p.Mul) + ((int64_t)(m0 + wm * 128) * p.N + n0 + wn * 64) * 2;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int row = jmap(j) * 32 + q * 8; // wave-uniform
+                const bool ok = interior || (n_ok && m0 + wm * 128 + row + (int)(ln >> 3) < p.M);
+                mv[q] = ok ? *reinterpret_cast<const uint4*>(mwave + (int64_t)row * p.N * 2 + dlane) : make_uint4(0u, 0u, 0u, 0u);
+            }
+        }
 #pragma unroll
         for (int q = 0; q < 4; ++q) v[q] = *reinterpret_cast<const uint4*>(wstg + q * 1024 + rd);
 #pragma unroll
@@ -740,6 +763,12 @@ __global__ __launch_bounds__(512) void gemm_w8a8o16_pp_kernel(const GemmParams p
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             if (q & 1) v[q] = uint4{v[q].z, v[q].w, v[q].x, v[q].y}; // rows with bit 3 set hold their 8-B halves swapped
+            if constexpr (MUL_LATE) { // gate * up: one bf16 multiply of the rounded values, in the layout they are stored in
+                v[q].x = __builtin_bit_cast(unsigned, omul2<true>(__builtin_bit_cast(v2h, v[q].x), mv[q].x));
+                v[q].y = __builtin_bit_cast(unsigned, omul2<true>(__builtin_bit_cast(v2h, v[q].y), mv[q].y));
+                v[q].z = __builtin_bit_cast(unsigned, omul2<true>(__builtin_bit_cast(v2h, v[q].z), mv[q].z));
+                v[q].w = __builtin_bit_cast(unsigned, omul2<true>(__builtin_bit_cast(v2h, v[q].w), mv[q].w));
+            }
             const int row = jmap(j) * 32 + q * 8;     // wave-uniform
             if constexpr (TP) {
                 const bool ok = interior || (n_ok && m0 + wm * 128 + row + (int)(ln >> 3) < p.M);
@@ -767,7 +796,7 @@ __global__ __launch_bounds__(512) void gemm_w8a8o16_pp_kernel(const GemmParams p
         for (int t = 0; t < 8; ++t) {
             if (SPLITK && t >= nt) break; // (uniform)
             v16f Pnext = Pcur;
-            if (t + 1 < nt) Pnext = side((t + 1) & 1, (t + 1) >> 1);
+            if (!P_BEHIND && t + 1 < nt) Pnext = side((t + 1) & 1, (t + 1) >> 1);
             if (EPI != EPI_F16GEMM && (t & 1) == 0) { // block j = t >> 1 starts: its row scale arrives, the next one is requested
                 sa_cur = o2f<BF>(sa_next);
                 if (t + 2 < nt) sa_next = load_sa((t >> 1) + 1);
@@ -782,6 +811,7 @@ __global__ __launch_bounds__(512) void gemm_w8a8o16_pp_kernel(const GemmParams p
             }
             dequant(t & 1, t >> 1, Pcur);
             if (S != 8 && (t & 1)) flush(t >> 1);
+            if (P_BEHIND && t + 1 < nt) Pnext = side((t + 1) & 1, (t + 1) >> 1);
             Pcur = Pnext;
             __builtin_amdgcn_sched_barrier(0);
         }

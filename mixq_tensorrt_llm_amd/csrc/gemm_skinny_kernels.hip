@@ -288,12 +288,12 @@ __global__ __launch_bounds__(KW * 64) void gemm_skinny_kernel(const GemmParams p
                 if (epi_has_silu(EPI)) v = silu_f32(v);
                 oh[e] = f2o_bits_of_f32_result<epi_bf16(EPI)>(v);
             }
-            if (EPI == EPI_DEQUANT_SILU_MUL) { // gate * up
+            if (epi_has_mul(EPI)) { // gate * up
                 const uint2 mb = *reinterpret_cast<const uint2*>(p.Mul + (int64_t)m * p.N + nb);
                 const uint16_t mh[4] = {(uint16_t)(mb.x & 0xffffu), (uint16_t)(mb.x >> 16), (uint16_t)(mb.y & 0xffffu),
                                         (uint16_t)(mb.y >> 16)};
 #pragma unroll
-                for (int e = 0; e < 4; ++e) oh[e] = f2h_bits(h2f(oh[e]) * h2f(mh[e]));
+                for (int e = 0; e < 4; ++e) oh[e] = omul_bits<epi_bf16(EPI)>(oh[e], mh[e]);
             }
             if constexpr (epi_bias(EPI)) { // the layer's bias: one fp16 (bf16) add of the rounded result
                 // (requested here, not with psw at kernel start: two registers more through the main loop cost the 17..32-row forms

@@ -797,7 +797,7 @@ int mixq_gemm_mixed(const int8_t* qA, const int8_t* W, const void* sA, const voi
 static int gemm_mixed_impl(const int8_t* qA, const int8_t* W, const void* sA, const void* sW, const void* fpA, const void* fpW,
                            void* Out, int M, int N, int K, int O, void* scratch, size_t scratch_bytes, void* stream,
                            int a_frag, const void* b_image = nullptr, bool image_resolved = false, const void* bias = nullptr,
-                           bool bf16 = false, const mixq::GemmPlan* plan = nullptr);
+                           bool bf16 = false, const mixq::GemmPlan* plan = nullptr, int act = 0, const void* mul = nullptr);
 
 int mixq_gemm_mixed_scratch(const int8_t* qA, const int8_t* W, const void* sA, const void* sW, const void* fpA,
                             const void* fpW, void* Out, int M, int N, int K, int O, void* scratch, size_t scratch_bytes,
@@ -815,9 +815,11 @@ int mixq_gemm_mixed_bias(const int8_t* qA, const int8_t* W, const void* sA, cons
     return gemm_mixed_impl(qA, W, sA, sW, fpA, fpW, Out, M, N, K, O, scratch, scratch_bytes, stream, 0, nullptr, false, bias);
 }
 
-// the epilogue of a mixed GEMM with 128 outlier columns at most
-static int mixed_epi(bool bias, bool bf16)
+// the epilogue of a mixed GEMM with 128 outlier columns at most (act: 0 | EPI_DEQUANT_SILU | EPI_DEQUANT_SILU_MUL, never with a bias)
+static int mixed_epi(bool bias, bool bf16, int act = 0)
 {
+    if (act == mixq::EPI_DEQUANT_SILU) return bf16 ? mixq::EPI_DEQUANT_SILU_BF16 : mixq::EPI_DEQUANT_SILU;
+    if (act == mixq::EPI_DEQUANT_SILU_MUL) return bf16 ? mixq::EPI_DEQUANT_SILU_MUL_BF16 : mixq::EPI_DEQUANT_SILU_MUL;
     return bf16 ? (bias ? mixq::EPI_DEQUANT_BIAS_BF16 : mixq::EPI_DEQUANT_BF16) : (bias ? mixq::EPI_DEQUANT_BIAS : mixq::EPI_DEQUANT);
 }
 
@@ -826,9 +828,11 @@ static int mixed_epi(bool bias, bool bf16)
 // b_image / image_resolved: the caller has already looked the weight's image up for this call (one lookup per call)
 // bias: the layer's fp16 [N] bias (EPI_DEQUANT_BIAS: the same kernel as EPI_DEQUANT, one fp16 add in its epilogue), or null
 // plan: mixq_enqueue has planned this call already (O == kNumOutliers, scratch sized by gemm_scratch_bytes), or null
+// act / mul: mixq_gemm_mixed_act_typed's activation (0 | EPI_DEQUANT_SILU | EPI_DEQUANT_SILU_MUL with its [M, N] multiplicand of the call's type)
 static int gemm_mixed_impl(const int8_t* qA, const int8_t* W, const void* sA, const void* sW, const void* fpA, const void* fpW,
                            void* Out, int M, int N, int K, int O, void* scratch, size_t scratch_bytes, void* stream,
-                           int a_frag, const void* b_image, bool image_resolved, const void* bias, bool bf16, const mixq::GemmPlan* plan)
+                           int a_frag, const void* b_image, bool image_resolved, const void* bias, bool bf16, const mixq::GemmPlan* plan,
+                           int act, const void* mul)
 {
     if (M < 0 || N < 0 || K <= 0 || O < 0) return MIXQ_E_BADARG;
     if (M == 0 || N == 0) return MIXQ_OK;
@@ -851,10 +855,11 @@ static int gemm_mixed_impl(const int8_t* qA, const int8_t* W, const void* sA, co
     if (O <= kNumOutliers) {
         p.fpA = static_cast<const uint16_t*>(fpA), p.fpW = static_cast<const uint16_t*>(fpW), p.O = O;
         p.bias = static_cast<const uint16_t*>(bias);
+        p.Mul = static_cast<const uint16_t*>(mul);
         g_last_gemm_bf16.store(bf16, std::memory_order_relaxed);
-        return hip_rc(mixq::launch_gemm(p, mixed_epi(bias != nullptr, bf16), st, plan));
+        return hip_rc(mixq::launch_gemm(p, mixed_epi(bias != nullptr, bf16, act), st, plan));
     }
-    if (bias || bf16) return MIXQ_E_SHAPE;
+    if (bias || bf16 || act) return MIXQ_E_SHAPE;
     // more outlier columns than one LDS pass holds: the reference's own two-step order (side GEMM into Out, then C = D = Out)
     hipError_t e = mixq::launch_gemm_fp16(fpA, fpW, Out, M, N, O, st);
     if (e != hipSuccess) return MIXQ_E_HIP;
@@ -983,6 +988,38 @@ int mixq_gemm_mixed_typed(const int8_t* qA, const int8_t* W, const void* sA, con
         if (!mixq::gemm_takes_skinny(probe, mixq::EPI_DEQUANT)) return MIXQ_E_SHAPE; // (the image has ONE reader)
     }
     return gemm_mixed_impl(qA, W, sA, sW, fpA, fpW, Out, M, N, K, O, scratch, scratch_bytes, stream, qa_layout, img, resolved, bias, bf16);
+}
+
+// mixq_gemm_mixed_typed with an activation in the epilogue of the SAME kernel (the plan is EPI_DEQUANT's): SiLU, or SiLU then one multiply
+// of the rounded value by `mul`.  The checks run by class -- type, arguments, shapes, alignment -- as the header states them.
+int mixq_gemm_mixed_act_typed(const int8_t* qA, const int8_t* W, const void* sA, const void* sW, const void* fpA, const void* fpW,
+                              const void* mul, void* Out, int M, int N, int K, int O, int epilogue, int qa_layout, int type,
+                              void* scratch, size_t scratch_bytes, void* stream)
+{
+    if (type != MIXQ_TYPE_HALF && type != MIXQ_TYPE_BF16) return MIXQ_E_TYPE;
+    const bool bf16 = type == MIXQ_TYPE_BF16;
+    if (epilogue != mixq::EPI_DEQUANT && epilogue != mixq::EPI_DEQUANT_SILU && epilogue != mixq::EPI_DEQUANT_SILU_MUL) return MIXQ_E_BADARG;
+    if ((epilogue == mixq::EPI_DEQUANT_SILU_MUL) != (mul != nullptr)) return MIXQ_E_BADARG;
+    if (mul && Out == mul) return MIXQ_E_BADARG; // (a lane's 16-byte fetch of mul covers elements other lanes store)
+    if (qa_layout != MIXQ_QA_ROW_MAJOR && qa_layout != MIXQ_QA_FRAGMENT_MAJOR) return MIXQ_E_BADARG;
+    if (M < 0 || N < 0 || K <= 0 || O < 0) return MIXQ_E_BADARG;
+    if (M == 0 || N == 0) return MIXQ_OK;
+    if (!qA || !W || !sA || !sW || !Out || (O > 0 && (!fpA || !fpW))) return MIXQ_E_BADARG;
+    if (K % 16 || N % 16 || O % 8) return MIXQ_E_SHAPE;
+    if (O > kNumOutliers && (epilogue != mixq::EPI_DEQUANT || bf16)) return MIXQ_E_SHAPE; // (one LDS pass of outlier columns: no addend form)
+    const void* img = nullptr;
+    bool resolved = false;
+    if (qa_layout == MIXQ_QA_FRAGMENT_MAJOR) {
+        if (O > kNumOutliers) return MIXQ_E_SHAPE;
+        img = mixq::resolve_weight_image(W, N, K, static_cast<hipStream_t>(stream));
+        resolved = true;
+        const size_t need = gemm_scratch_bytes(M, N, K);
+        const mixq::GemmParams probe = plan_probe(M, N, K, O, 1, scratch && need && scratch_bytes >= need ? scratch : nullptr, img);
+        if (!mixq::gemm_takes_skinny(probe, mixq::EPI_DEQUANT)) return MIXQ_E_SHAPE; // (the image has ONE reader)
+    }
+    if (mul && !aligned16(mul)) return MIXQ_E_ALIGN; // (the ping-pong kernels fetch it 16 bytes at a time)
+    return gemm_mixed_impl(qA, W, sA, sW, fpA, fpW, Out, M, N, K, O, scratch, scratch_bytes, stream, qa_layout, img, resolved, nullptr, bf16,
+                           nullptr, epilogue, mul);
 }
 
 int mixq_mixlinear_forward(int M, int N, int K, int O, void* x, const int32_t* ind, const int8_t* q_weight,

@@ -116,6 +116,13 @@ __device__ __forceinline__ uint16_t oadd_bits(uint16_t a, uint16_t b)
     if constexpr (BF) return f2bf_bits(bf2f(a) + bf2f(b));
     else return hadd_bits(a, b);
 }
+// 16-bit x 16-bit of the output type, rounded once (gate * up; the fp32 product of two fp16 or two bf16 values is exact)
+template <bool BF>
+__device__ __forceinline__ uint16_t omul_bits(uint16_t a, uint16_t b)
+{
+    if constexpr (BF) return f2bf_bits(bf2f(a) * bf2f(b));
+    else return f2h_bits(h2f(a) * h2f(b));
+}
 
 // Two fp32 results -> packed fp16 (RNE), both pinned first (same reason); one v_cvt_pk_f16_f32.
 __device__ __forceinline__ v2h f2h2_of_f32_results(float a, float b)
@@ -136,6 +143,15 @@ __device__ __forceinline__ v2h bf2_add(v2h a, unsigned b)
 {
     const unsigned u = __builtin_bit_cast(unsigned, a);
     return f2bf2_of_f32_results(bf2f((uint16_t)(u & 0xffffu)) + bf2f((uint16_t)(b & 0xffffu)), bf2f((uint16_t)(u >> 16)) + bf2f((uint16_t)(b >> 16)));
+}
+// a packed pair of the output type x the pair b, each rounded once (gate * up of the packed epilogues; fp16: one v_pk_mul_f16)
+template <bool BF>
+__device__ __forceinline__ v2h omul2(v2h a, unsigned b)
+{
+    if constexpr (BF) {
+        const unsigned u = __builtin_bit_cast(unsigned, a);
+        return f2bf2_of_f32_results(bf2f((uint16_t)(u & 0xffffu)) * bf2f((uint16_t)(b & 0xffffu)), bf2f((uint16_t)(u >> 16)) * bf2f((uint16_t)(b >> 16)));
+    } else return a * __builtin_bit_cast(v2h, b);
 }
 template <bool BF>
 __device__ __forceinline__ v2h f2o2_of_f32_results(float a, float b)

@@ -46,10 +46,18 @@ enum { EPI_DEQUANT = 0, EPI_DEQUANT_SILU = 1, EPI_INT32 = 2, EPI_DEQUANT_SILU_MU
 // and D are bf16; the outlier product runs on the bf16 MFMA and is rounded to bf16, D = bf16(fma(acc, sW sA, P)) (+ one bf16 add of
 // the bias).  sW stays fp16.  Kernel choice: the same as EPI_DEQUANT
 enum { EPI_DEQUANT_BF16 = 6, EPI_DEQUANT_BIAS_BF16 = 7 };
-constexpr bool epi_has_silu(int epi) { return epi == EPI_DEQUANT_SILU || epi == EPI_DEQUANT_SILU_MUL; }
-constexpr bool epi_bf16(int epi) { return epi == EPI_DEQUANT_BF16 || epi == EPI_DEQUANT_BIAS_BF16; }
+// 8 / 9: EPI_DEQUANT_SILU / EPI_DEQUANT_SILU_MUL of a bf16 call (mixq_gemm_mixed_act_typed): g = bf16(silu(fma(acc, sW sA, P))) on the fp32
+// value, D = g or D = bf16(fp32(g) * fp32(Mul)) -- one multiply of the ROUNDED g by the bf16 [M,N] multiplicand (the fp32 product of two bf16
+// values is exact: one rounding, torch's bf16 multiply).  No addend, no bias, no peer writes, O <= 128.  Kernel choice: the same as EPI_DEQUANT
+enum { EPI_DEQUANT_SILU_BF16 = 8, EPI_DEQUANT_SILU_MUL_BF16 = 9 };
+constexpr bool epi_has_mul(int epi) { return epi == EPI_DEQUANT_SILU_MUL || epi == EPI_DEQUANT_SILU_MUL_BF16; }
+constexpr bool epi_has_silu(int epi) { return epi == EPI_DEQUANT_SILU || epi == EPI_DEQUANT_SILU_BF16 || epi_has_mul(epi); }
+constexpr bool epi_bf16(int epi)
+{
+    return epi == EPI_DEQUANT_BF16 || epi == EPI_DEQUANT_BIAS_BF16 || epi == EPI_DEQUANT_SILU_BF16 || epi == EPI_DEQUANT_SILU_MUL_BF16;
+}
 constexpr bool epi_bias(int epi) { return epi == EPI_DEQUANT_BIAS || epi == EPI_DEQUANT_BIAS_BF16; }
-// f(std::integral_constant<int, EPI>{}) with the run-time `epi` as a compile-time constant: the six dequantising epilogues; any other
+// f(std::integral_constant<int, EPI>{}) with the run-time `epi` as a compile-time constant: the eight dequantising epilogues; any other
 // value is EPI_INT32 where the family has that build (INT32), else an error (and f is not instantiated for it)
 template <bool INT32, class F>
 inline hipError_t with_epi(int epi, F&& f)
@@ -61,6 +69,8 @@ inline hipError_t with_epi(int epi, F&& f)
     case EPI_DEQUANT_BIAS: return f(std::integral_constant<int, EPI_DEQUANT_BIAS>{});
     case EPI_DEQUANT_BF16: return f(std::integral_constant<int, EPI_DEQUANT_BF16>{});
     case EPI_DEQUANT_BIAS_BF16: return f(std::integral_constant<int, EPI_DEQUANT_BIAS_BF16>{});
+    case EPI_DEQUANT_SILU_BF16: return f(std::integral_constant<int, EPI_DEQUANT_SILU_BF16>{});
+    case EPI_DEQUANT_SILU_MUL_BF16: return f(std::integral_constant<int, EPI_DEQUANT_SILU_MUL_BF16>{});
     }
     if constexpr (INT32) return f(std::integral_constant<int, EPI_INT32>{});
     else return hipErrorInvalidValue;
@@ -94,7 +104,7 @@ struct GemmParams {
     const uint16_t* fpA;  // [M,O] or null
     const uint16_t* fpW;  // [N,O] or null
     const uint16_t* Y;    // fp16 [M,N] addend or null (int8FusedDequantize API)
-    const uint16_t* Mul;  // fp16 [M,N] multiplicand of EPI_DEQUANT_SILU_MUL: D = fp16(fp16(silu(..)) * Mul), else null
+    const uint16_t* Mul;  // fp16 (bf16) [M,N] multiplicand of EPI_DEQUANT_SILU_MUL (_BF16): D = fp16(fp16(silu(..)) * Mul), else null
     void* D;              // fp16 [M,N] (EPI_DEQUANT*) or int32 [M,N] (EPI_INT32)
     const void* zeros;    // >= 16 B of device zeros (K / O tails)
     int M, N, K, O;

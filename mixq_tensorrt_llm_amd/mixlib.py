@@ -620,27 +620,45 @@ def mixq_linear(A, W_int8, sW, fp_weight, ind, out=None, workspace=None):
 
 
 @_on_tensor_device
-def gemm_mixed(q, W_int8, x_scale, sW, outliers, fp_weight, M, N, K, bias=None, qa_layout=0, out=None):
+def gemm_mixed(q, W_int8, x_scale, sW, outliers, fp_weight, M, N, K, bias=None, qa_layout=0, out=None, act=None, mul=None):
     """MI355X extension (``mixq_gemm_mixed_typed``): the fused GEMM on a producer's output -- ``q`` int8 rows (or the
     fragment-major image, ``qa_layout``), ``x_scale`` [M], ``outliers`` [M, O] as ``layernorm_forward_cuda_extract_outliers``
     leaves them -- with W int8 [N, K], ``sW`` fp16 [N], ``fp_weight`` [N, O] and an optional ``bias`` [N] added in the epilogue.
     fp16 or bf16: the type is ``outliers``' (``x_scale``'s when there are no outlier columns); ``x_scale``, ``fp_weight``, ``bias``
-    and ``out`` must have it, ``sW`` stays fp16.  Returns ``out`` [M, N] (allocated unless given)."""
+    and ``out`` must have it, ``sW`` stays fp16.  Returns ``out`` [M, N] (allocated unless given).
+
+    ``act="silu"`` (``mixq_gemm_mixed_act_typed``) applies SiLU in the same launch's epilogue, ``mul`` ([M, N] of the call's type, not
+    ``out``) then multiplies the rounded result: the gate projection of an MLP, ``silu(gate(x)) * up(x)``, as one launch.  No bias with
+    ``act``."""
+    if act not in (None, "silu"):
+        raise ValueError(f"gemm_mixed: act is {act!r}; None and 'silu' are supported")
+    if mul is not None and act is None:
+        raise ValueError("gemm_mixed: mul is the multiplicand of act='silu' and needs it")
+    if act is not None and bias is not None:
+        raise ValueError("gemm_mixed: the SiLU epilogues take no bias")
     O = 0 if outliers is None else int(outliers.shape[-1])
     dt = outliers.dtype if O else x_scale.dtype
     if dt not in (torch.float16, torch.bfloat16):
         raise TypeError(f"gemm_mixed: the activation type is {dt}; fp16 and bf16 are supported")
-    for name, t in (("x_scale", x_scale), ("fp_weight", fp_weight if O else None), ("bias", bias), ("out", out)):
+    for name, t in (("x_scale", x_scale), ("fp_weight", fp_weight if O else None), ("bias", bias), ("out", out), ("mul", mul)):
         if t is not None and t.dtype != dt:
-            raise TypeError(f"gemm_mixed: {name} is {t.dtype} in a {_act_name(dt)} call (x_scale, outliers, fp_weight, bias and out share one type)")
+            raise TypeError(f"gemm_mixed: {name} is {t.dtype} in a {_act_name(dt)} call (x_scale, outliers, fp_weight, bias, mul and out share one type)")
+    if mul is not None and (mul.numel() != M * N or mul is out or (out is not None and mul.data_ptr() == out.data_ptr())):
+        raise ValueError(f"gemm_mixed: mul holds {mul.numel()} elements ({M} x {N} needed) and must not be out")
     if sW.dtype != torch.float16 or q.dtype != torch.int8 or W_int8.dtype != torch.int8:
         raise TypeError("gemm_mixed: q and W_int8 are int8, sW is fp16")
-    _dev(*(t for t in (q, W_int8, x_scale, sW, outliers if O else None, fp_weight if O else None, bias, out) if t is not None))
+    _dev(*(t for t in (q, W_int8, x_scale, sW, outliers if O else None, fp_weight if O else None, bias, out, mul) if t is not None))
     _rows_fit(x_scale, M, "gemm_mixed")
     if out is None:
         out = torch.empty((M, N), dtype=dt, device=q.device)
     assert out.numel() == M * N and (bias is None or bias.numel() == N) and sW.numel() >= N
     scr = None if qa_layout else gemm_scratch(q, M, N, K)
+    if act is not None:
+        _lib.check(_lib.load().mixq_gemm_mixed_act_typed(_p(q), _p(W_int8), _p(x_scale), _p(sW), _p(outliers) if O else None,
+                                                         _p(fp_weight) if O else None, _p(mul), _p(out), M, N, K, O, 1 if mul is None else 3,
+                                                         qa_layout, _lib.MIXQ_TYPE_BF16 if dt == torch.bfloat16 else _lib.MIXQ_TYPE_HALF,
+                                                         _p(scr), scr.numel() if scr is not None else 0, _st(q)), "gemm_mixed")
+        return out
     _lib.check(_lib.load().mixq_gemm_mixed_typed(_p(q), _p(W_int8), _p(x_scale), _p(sW), _p(outliers) if O else None,
                                                  _p(fp_weight) if O else None, _p(bias), _p(out), M, N, K, O, qa_layout,
                                                  _lib.MIXQ_TYPE_BF16 if dt == torch.bfloat16 else _lib.MIXQ_TYPE_HALF, _p(scr),

@@ -300,7 +300,7 @@ class MixQLinear:
         """The outlier columns as the producers take them: the int32 [128] view of ``fp_ind``."""
         return self.fp_ind.view(torch.int32)
 
-    def forward_quantised(self, q, x_scale, outliers, q_layout: int = 0, lead_shape=None) -> torch.Tensor:
+    def forward_quantised(self, q, x_scale, outliers, q_layout: int = 0, lead_shape=None, act=None, mul=None) -> torch.Tensor:
         """MI355X extension: this layer's GEMM on what a fused norm producer has already written -- int8 rows ``q`` (row-major, or the
         fragment-major image with ``q_layout``), row scales ``x_scale`` and ``outliers`` [M, 128], in the layer's dtype -- through
         ``mixlib.gemm_mixed`` (``mixq_gemm_mixed_typed``) with the bias in the epilogue.  No quantiser pass and no second read of the
@@ -309,16 +309,53 @@ class MixQLinear:
             n, h = norm.forward_residual(x, residual)
             y = linear.forward_quantised(cache.q_xcache, cache.x_scale, cache.activation_outliers, cache.q_layout)
 
-        ``lead_shape``: the leading dimensions of the result (default: [M])."""
+        ``lead_shape``: the leading dimensions of the result (default: [M]).  ``act="silu"`` / ``mul``: SiLU, then a multiply by ``mul``
+        [M, N], in the same launch's epilogue (``mixlib.gemm_mixed``); a layer with a bias refuses them."""
         from . import mixlib
         if self.tp_size > 1:
             raise ValueError("MixQLinear.forward_quantised: a row-sharded layer (tp_size > 1) has no producer-fed path")
+        if act not in (None, "silu"):
+            raise ValueError(f"MixQLinear.forward_quantised: act is {act!r}; None and 'silu' are supported")
+        if mul is not None and act is None:
+            raise ValueError("MixQLinear.forward_quantised: mul is the multiplicand of act='silu' and needs it")
+        if act is not None and self.bias is not None:
+            raise ValueError("MixQLinear.forward_quantised: the SiLU epilogues take no bias, and this layer has one")
         if outliers.dtype != self.dtype or x_scale.dtype != self.dtype:
             raise TypeError(f"MixQLinear.forward_quantised: a {self.dtype} layer got {outliers.dtype} outliers and {x_scale.dtype} row scales")
         M = outliers.shape[0]
         bias = None if self.bias is None else fp16_bias(self.bias, self.out_features, outliers.device, self.dtype)
         y = mixlib.gemm_mixed(q, self.weight.view(torch.int8), x_scale, self.weights_scaling_factor, outliers, self.fp_weight, M,
-                              self.out_features, self.in_features, bias=bias, qa_layout=q_layout)
+                              self.out_features, self.in_features, bias=bias, qa_layout=q_layout, act=act,
+                              mul=None if mul is None else mul.reshape(M, self.out_features))
         return y if lead_shape is None else y.reshape(*lead_shape, self.out_features)
 
     __call__ = forward
+
+
+class MixQLlamaMLP:
+    """MI355X extension: ``down(silu(gate(x)) * up(x))`` of a Llama MLP on what ONE fused norm producer pass has written.  The up projection
+    is one launch, the gate projection -- outlier product, SiLU and the multiply by ``up`` in its epilogue -- another, and ``down`` quantises
+    its own input (``MixQLinear.forward``).  fp16 or bf16, the layers' ``dtype``.
+
+    ``gate`` and ``up`` read the same int8 rows, row scales and outlier columns: they must share ``dtype``, ``in_features``, ``out_features``
+    and an identical ``fp_ind``; neither has a bias, and none of the three layers is row-sharded (``ValueError`` otherwise)."""
+
+    def __init__(self, gate: MixQLinear, up: MixQLinear, down: MixQLinear):
+        for name in ("dtype", "in_features", "out_features"):
+            if getattr(gate, name) != getattr(up, name):
+                raise ValueError(f"MixQLlamaMLP: gate and up differ in {name} ({getattr(gate, name)} vs {getattr(up, name)}); one producer pass feeds both")
+        if down.dtype != gate.dtype:
+            raise ValueError(f"MixQLlamaMLP: down is {down.dtype}, gate and up are {gate.dtype}")
+        if gate.fp_ind.shape != up.fp_ind.shape or not torch.equal(gate.fp_ind.view(torch.int32).cpu(), up.fp_ind.view(torch.int32).cpu()):
+            raise ValueError("MixQLlamaMLP: gate and up have different outlier columns (fp_ind); one producer pass feeds both")
+        if gate.bias is not None or up.bias is not None:
+            raise ValueError("MixQLlamaMLP: gate and up must have no bias (the SiLU epilogues take none)")
+        if gate.tp_size > 1 or up.tp_size > 1 or down.tp_size > 1:
+            raise ValueError("MixQLlamaMLP: a row-sharded layer (tp_size > 1) has no producer-fed path")
+        self.gate, self.up, self.down = gate, up, down
+
+    def forward_quantised(self, q, x_scale, outliers, q_layout: int = 0, lead_shape=None) -> torch.Tensor:
+        u = self.up.forward_quantised(q, x_scale, outliers, q_layout)
+        g = self.gate.forward_quantised(q, x_scale, outliers, q_layout, act="silu", mul=u)
+        y = self.down(g)
+        return y if lead_shape is None else y.reshape(*lead_shape, self.down.out_features)
