@@ -157,7 +157,9 @@ MIXQ_API int mixq_int8quant(int rows, int cols, const void* src_f16, int8_t* out
 /* ExtractOutliersAndSetToZeros (kernel/i8gemm.cu:226-244): fp_A[m,j] = A[m,ind[j]]; A is NOT modified (T-flavour). */
 MIXQ_API int mixq_extract_outliers(int M, int K, const void* A_f16, void* fpA_f16, const int32_t* ind, int len,
                                    void* stream);
-/* mixlib twin (quantkernel/mix_cuda/cult.cu:1406-1465): same gather, then writes 0 into A (P-flavour). */
+/* mixlib twin (quantkernel/mix_cuda/cult.cu:1406-1465): same gather, then writes 0 into A (P-flavour).
+ * Both gathers are 2-byte BIT COPIES (and the zero is 0x0000): they serve bf16 rows unchanged, there is no typed form.  Every ind[j]
+ * must lie in [0, K) here (the -1 padding of a bf16 P-flavour set is defined by the typed producers only). */
 MIXQ_API int mixq_extract_outliers_set_zero(int M, int K, void* A_f16, void* fpA_f16, const int32_t* ind, int len,
                                             void* stream);
 /* The fused producer this implementation actually runs in enqueue: one pass over A producing qA, sA and fpA.
@@ -373,6 +375,46 @@ MIXQ_API int mixq_mixlinear_forward(int M, int N, int K, int O, void* x_f16, con
                                     const void* scale_col, const void* weight_cache, void* x_scale, int8_t* q_x,
                                     void* outliers_f16, void* out_f16, int q_layout, void* scratch, size_t scratch_bytes,
                                     void* stream);
+/* ---- typed forms of the P-flavour's entries (MI355X extension): fp16 or bf16 rows ------------------------------------------------
+ * The reference's PyTorch-package flavour (MixQ/src/mixquant/modules/linear.py) is fp16 only.  For each entry below `type` is
+ * MIXQ_TYPE_HALF or MIXQ_TYPE_BF16, anything else returns MIXQ_E_TYPE before every other check, and MIXQ_TYPE_HALF IS the named fp16
+ * entry: same bits, same codes in the same order, same launch.  MIXQ_TYPE_BF16, IEEE fp32 arithmetic as written:
+ *
+ * mixq_quant_extract_typed = mixq_quant_extract_layout on bf16 A / sA / fpA, in the form (threads per row, vectors per lane, grid, LDS
+ * mask, non-temporal threshold) the fp16 call takes for the same (M, K, q_layout, zero_outliers).  Per row m:
+ *   fpA[m,j] = A[m, ind[j]]            a bit copy of the ORIGINAL value; ind[j] outside [0, K): +0, and nothing is zeroed
+ *   z        = the row (zero_outliers: with the columns {ind[j] in [0, K)} replaced by +0, written back to A)
+ *   sA[m]    = bf16_rn(float(amax) / 127)                       amax = max |z|, NaNs dropped; an all-NaN row gives NaN
+ *   q[m,k]   = sat[-127, 127](rint(float(z[k]) / float(sA[m])))  a NaN quotient gives 0
+ * zero_outliers = 0 is the quantiser a bf16 mixq_enqueue runs; zero_outliers = 1 is bit-identical to mixq_extract_outliers_set_zero
+ * followed by the zero_outliers = 0 call with len = 0.  mixq_debug_last_producer_kernel reports the fp16 form's name + " [bf16]"
+ * (" nt" behind it where it applies).
+ *
+ * mixq_find_outliers_typed = mixq_find_outliers on bf16 A: column k is reported iff some row has |float(a)| > sigma (NaN compares
+ * false, +-inf true) -- torch.where(A.abs() > sigma) with a bf16 A and an fp16 sigma tensor, which torch promotes to fp32.  Same
+ * workspace size, grid and compaction.
+ *
+ * mixq_dequant_weight_columns_typed: out[n,j] = bf16_rn(float(q_weight[n, ind[j]]) * float(scale_col[n])), out bf16 [N, len];
+ * scale_col stays fp16 (the fp32 product of an int8 and an fp16 value is exact: one rounding); ind[j] outside [0, K): a zero column.
+ *
+ * mixq_mixlinear_forward_typed = mixq_mixlinear_forward with x, weight_cache, x_scale, outliers and out bf16 (scale_col fp16): TWO
+ * launches, the zeroing quantiser above and what mixq_gemm_mixed_typed(.., bias = NULL, MIXQ_TYPE_BF16) launches for the shape, so
+ *   out = bf16_rn(fma(acc, sW sA, bf16_rn(sum_j float(fpA[m,j]) float(weight_cache[n,j]))))   on the zeroed row's q / sA.
+ * ind[j] = -1 is allowed (a zero outlier column: the padding of a set to a multiple of 8).  Unlike the fp16 entry, which launches its
+ * quantiser before the GEMM's checks run, the bf16 call makes EVERY refusal before anything is launched, so a refused call leaves x
+ * untouched: MIXQ_E_BADARG (a negative size, a null operand, a bad q_layout), then MIXQ_E_SHAPE (O % 8, O > 128 -- the bf16 epilogues
+ * have no addend form --, K % 16, N % 16, K % 8, a fragment-major image where mixq_qa_layout does not say so), then MIXQ_E_ALIGN (x,
+ * q_x, q_weight, scale_col, weight_cache, outliers, out: 16 bytes).  M == 0 or N == 0 returns MIXQ_OK without touching the device.
+ * Asynchronous, no allocation, capturable. */
+MIXQ_API int mixq_quant_extract_typed(int M, int K, void* A, int8_t* qA, void* sA, void* fpA, const int32_t* ind, int len,
+                                      int zero_outliers, int q_layout, int type, void* stream);
+MIXQ_API int mixq_find_outliers_typed(const void* A, int M, int K, float sigma, void* mask_ws, int32_t* ind_out, int32_t* count_out,
+                                      int capacity, int type, void* stream);
+MIXQ_API int mixq_dequant_weight_columns_typed(const int8_t* q_weight, const void* scale_col_f16, const int32_t* ind, int len, void* out,
+                                               int N, int K, int type, void* stream);
+MIXQ_API int mixq_mixlinear_forward_typed(int M, int N, int K, int O, void* x, const int32_t* ind, const int8_t* q_weight,
+                                          const void* scale_col, const void* weight_cache, void* x_scale, int8_t* q_x, void* outliers,
+                                          void* out, int q_layout, int type, void* scratch, size_t scratch_bytes, void* stream);
 /* gemm (TsinghuaMixQPlugin.cpp:36-77, cuBLAS s8 x s8 -> s32): raw int32 accumulators, for bit-exact checks. */
 MIXQ_API int mixq_gemm_s8s8s32(const int8_t* A, const int8_t* B, int32_t* C, int M, int N, int K, void* stream);
 /* gemmfp16 (TsinghuaMixQPlugin.cpp:122-161): Out = fpA . fpW^T, fp32 accumulate, fp16 out. */
@@ -631,7 +673,8 @@ MIXQ_API const char* mixq_version(void);
  * header can refuse to run instead of passing shifted arguments: `if (mixq_abi_version() != MIXQ_ABI_VERSION) fail`.  The
  * reference-named entries (initOpenAiTritonPlugins, the plugin lifecycle, mixq_enqueue) have not changed since revision 1.
  * Revision 5 adds entries only (mixq_enqueue_bias, mixq_enqueue_tp_bias, mixq_gemm_mixed_bias; later, still 5: mixq_add_rmsnorm*,
- * mixq_rmsnorm_typed, mixq_rmsnorm_extract_quant_typed, mixq_gemm_mixed_typed, mixq_gemm_mixed_act_typed). */
+ * mixq_rmsnorm_typed, mixq_rmsnorm_extract_quant_typed, mixq_gemm_mixed_typed, mixq_gemm_mixed_act_typed, mixq_quant_extract_typed,
+ * mixq_find_outliers_typed, mixq_dequant_weight_columns_typed, mixq_mixlinear_forward_typed). */
 #define MIXQ_ABI_VERSION 5
 MIXQ_API int mixq_abi_version(void);
 MIXQ_API const char* mixq_error_string(int code);

@@ -127,6 +127,10 @@ SIGNATURES = {
     "mixq_int8_fused_dequantize_silu_mul": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
     "mixq_gemm_mixed": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "mixq_mixlinear_forward": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, ctypes.c_size_t, _vp]),
+    "mixq_mixlinear_forward_typed": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, ctypes.c_size_t, _vp]),
+    "mixq_quant_extract_typed": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "mixq_find_outliers_typed": (_i, [_vp, _i, _i, ctypes.c_float, _vp, _vp, _vp, _i, _i, _vp]),
+    "mixq_dequant_weight_columns_typed": (_i, [_vp, _vp, _vp, _i, _vp, _i, _i, _i, _vp]),
     "mixq_qa_layout": (_i, [_i, _i, _i]),
     "mixq_qa_bytes": (ctypes.c_size_t, [_i, _i, _i]),
     "mixq_quant_extract_layout": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),

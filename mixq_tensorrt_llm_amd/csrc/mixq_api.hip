@@ -1050,6 +1050,72 @@ int mixq_mixlinear_forward(int M, int N, int K, int O, void* x, const int32_t* i
                                       stream);
 }
 
+// ---- typed forms of the P-flavour's entries (MI355X extension): fp16 = the named entry, bf16 = its checks in its order on bf16 rows ----
+int mixq_quant_extract_typed(int M, int K, void* A, int8_t* qA, void* sA, void* fpA, const int32_t* ind, int len, int zero_outliers,
+                             int q_layout, int type, void* stream)
+{
+    if (!norm_type_ok(type)) return MIXQ_E_TYPE;
+    if (type == MIXQ_TYPE_HALF) return mixq_quant_extract_layout(M, K, A, qA, sA, fpA, ind, len, zero_outliers, q_layout, stream);
+    const bool frag = q_layout == MIXQ_QA_FRAGMENT_MAJOR;
+    if (q_layout != MIXQ_QA_ROW_MAJOR && !frag) return MIXQ_E_BADARG;
+    if (M < 0 || K <= 0 || len < 0 || (M > 0 && (!A || !qA || !sA))) return MIXQ_E_BADARG;
+    if (len > 0 && (!fpA || !ind)) return MIXQ_E_BADARG;
+    if (K % 8 || (frag && !mixq::quant_frag_layout_supported(M, K))) return MIXQ_E_SHAPE;
+    if (!aligned16(A) || (reinterpret_cast<uintptr_t>(qA) & (frag ? 15u : 7u))) return MIXQ_E_ALIGN;
+    return hip_rc(mixq::launch_quant_extract(A, qA, sA, len > 0 ? fpA : nullptr, ind, M, K, len, zero_outliers != 0,
+                                             static_cast<hipStream_t>(stream), nullptr, frag ? 1 : 0, true));
+}
+
+int mixq_find_outliers_typed(const void* A, int M, int K, float sigma, void* mask_ws, int32_t* ind_out, int32_t* count_out, int capacity,
+                             int type, void* stream)
+{
+    if (!norm_type_ok(type)) return MIXQ_E_TYPE;
+    if (type == MIXQ_TYPE_HALF) return mixq_find_outliers(A, M, K, sigma, mask_ws, ind_out, count_out, capacity, stream);
+    if (M < 0 || K <= 0 || capacity < 0 || !mask_ws || !count_out || (capacity > 0 && !ind_out) || (M > 0 && !A))
+        return MIXQ_E_BADARG;
+    if (K % 8) return MIXQ_E_SHAPE;
+    if (M > 0 && !aligned16(A)) return MIXQ_E_ALIGN;
+    return hip_rc(mixq::launch_find_outliers(A, M, K, sigma, static_cast<unsigned*>(mask_ws), ind_out, count_out, capacity,
+                                             static_cast<hipStream_t>(stream), true));
+}
+
+int mixq_dequant_weight_columns_typed(const int8_t* q_weight, const void* scale_col, const int32_t* ind, int len, void* out, int N, int K,
+                                      int type, void* stream)
+{
+    if (!norm_type_ok(type)) return MIXQ_E_TYPE;
+    if (type == MIXQ_TYPE_HALF) return mixq_dequant_weight_columns(q_weight, scale_col, ind, len, out, N, K, stream);
+    if (N < 0 || K <= 0 || len < 0 || (N > 0 && len > 0 && (!q_weight || !scale_col || !ind || !out)))
+        return MIXQ_E_BADARG;
+    return hip_rc(mixq::launch_dequant_columns(q_weight, scale_col, ind, len, out, N, K, static_cast<hipStream_t>(stream), true));
+}
+
+int mixq_mixlinear_forward_typed(int M, int N, int K, int O, void* x, const int32_t* ind, const int8_t* q_weight, const void* scale_col,
+                                 const void* weight_cache, void* x_scale, int8_t* q_x, void* outliers, void* out, int q_layout, int type,
+                                 void* scratch, size_t scratch_bytes, void* stream)
+{
+    if (!norm_type_ok(type)) return MIXQ_E_TYPE;
+    if (type == MIXQ_TYPE_HALF)
+        return mixq_mixlinear_forward(M, N, K, O, x, ind, q_weight, scale_col, weight_cache, x_scale, q_x, outliers, out, q_layout, scratch,
+                                      scratch_bytes, stream);
+    // bf16: the zeroing quantiser on bf16 rows, then what mixq_gemm_mixed_typed(.., bias = NULL, MIXQ_TYPE_BF16) launches.  The first launch
+    // writes x, so EVERY refusal of either step is made here, before it: a refused call leaves x as it was.
+    const bool frag = q_layout == MIXQ_QA_FRAGMENT_MAJOR;
+    if (M < 0 || N < 0 || K <= 0 || O < 0 || (q_layout != MIXQ_QA_ROW_MAJOR && !frag)) return MIXQ_E_BADARG;
+    if (M == 0 || N == 0) return MIXQ_OK;
+    if (!x || !q_weight || !scale_col || !x_scale || !q_x || !out || (O > 0 && (!ind || !weight_cache || !outliers)))
+        return MIXQ_E_BADARG;
+    if (O % 8 != 0 || O > kNumOutliers) return MIXQ_E_SHAPE; // (one LDS pass of outlier columns: the bf16 epilogues take no addend)
+    if (K % 16 || N % 16 || K % 8) return MIXQ_E_SHAPE;
+    if (frag && mixq_qa_layout(M, N, K) != MIXQ_QA_FRAGMENT_MAJOR) return MIXQ_E_SHAPE;
+    if (!aligned16(x) || !aligned16(q_x) || !aligned16(q_weight) || !aligned16(out) || !aligned16(scale_col) || (O > 0 && (!aligned16(outliers) || !aligned16(weight_cache))))
+        return MIXQ_E_ALIGN;
+    int rc = hip_rc(mixq::launch_quant_extract(x, q_x, x_scale, O > 0 ? outliers : nullptr, ind, M, K, O, true,
+                                               static_cast<hipStream_t>(stream), nullptr, frag ? 1 : 0, true));
+    if (rc != MIXQ_OK) return rc;
+    return mixq_gemm_mixed_typed(q_x, q_weight, x_scale, scale_col, outliers, weight_cache, nullptr, out, M, N, K, O, q_layout,
+                                 MIXQ_TYPE_BF16, frag ? nullptr : scratch, frag ? 0 : scratch_bytes, stream);
+}
+
 int mixq_gemm_s8s8s32(const int8_t* A, const int8_t* B, int32_t* C, int M, int N, int K, void* stream)
 {
     if (M < 0 || N < 0 || K <= 0) return MIXQ_E_BADARG;

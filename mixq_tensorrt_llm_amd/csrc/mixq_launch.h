@@ -222,7 +222,8 @@ hipError_t launch_quant_extract(void* A, int8_t* qA, void* sA, void* fpA, const 
                                 bool zero, hipStream_t st,
                                 void* zero_words = nullptr, // (kSplitkWordsBytes to clear on the way, or null)
                                 int frag = 0,  // qA layout: 0 row-major | 1 the skinny GEMM's fragment order (quant_frag_layout_supported)
-                                bool bf16 = false); // A, sA, fpA are bf16 (zero == false only): sA = bf16(amax / 127), q = sat(rint(x / sA))
+                                bool bf16 = false); // A, sA, fpA are bf16 (either flavour): sA = bf16(amax / 127), q = sat(rint(x / sA)) on the
+                                                    // row as quantised (zero: the zeroed row); an ind[j] outside [0, K) gathers +0, zeroes nothing
 void set_quant_block_rows(int m); // measurement knob 1300 (rules) / 1301..1312 (64 << n rows)
 int quant_block_rows(int nvec, bool norm_producer); // rows up to which a whole 256-thread block takes one row of nvec 16-byte vectors
 bool quant_frag_layout_supported(int M, int K);   // the quantiser can write the fragment-major image for this shape
@@ -246,9 +247,9 @@ hipError_t launch_rmsnorm_quant(const void* X, const void* gamma, void* out, voi
                                 // scale = bf16(amax / 127), q = sat(rint(out / scale)) -- launch_quant_extract's bf16 rules on the rounded row
                                 bool bf16 = false);
 hipError_t launch_find_outliers(const void* A, int M, int K, float sigma, unsigned* mask, int32_t* ind, int32_t* count,
-                                int capacity, hipStream_t st);
+                                int capacity, hipStream_t st, bool bf16 = false); // bf16: A is bf16 (|fp32(a)| > sigma)
 hipError_t launch_dequant_columns(const int8_t* W, const void* sW, const int32_t* ind, int len, void* out, int N, int K,
-                                  hipStream_t st);
+                                  hipStream_t st, bool bf16 = false); // bf16: out is bf16 (sW stays fp16); ind[j] outside [0, K): a zero column
 hipError_t launch_quant4_rows(const void* A, uint8_t* q, void* sA, int M, int K, hipStream_t st);
 hipError_t launch_unpack_s4(const uint8_t* src, int8_t* dst, size_t packed_bytes, hipStream_t st);
 // packed-int4 weight stream (int4_gemm_kernels.hip): p.A / p.B packed int4 [M, K] / [N, K], p.K = PACKED bytes per row, p.Y addend or null

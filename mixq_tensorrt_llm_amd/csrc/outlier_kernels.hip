@@ -16,6 +16,8 @@ constexpr int OBLOCK = 256;
 
 // Each thread owns 8 consecutive columns (one 16-byte vector) and walks down `rows_per_block` rows; column flags are
 // merged through LDS and pushed to the global mask with at most one atomicOr per 32 columns per block.
+// BF: A is bf16; |fp32(a)| > sigma with the fp32 sigma (torch promotes bf16 A against an fp16 sigma tensor to fp32)
+template <bool BF>
 __global__ __launch_bounds__(OBLOCK) void outlier_flags_kernel(const uint16_t* __restrict__ A, unsigned* __restrict__ mask,
                                                                int M, int K, float sigma, int rows_per_block)
 {
@@ -31,8 +33,8 @@ __global__ __launch_bounds__(OBLOCK) void outlier_flags_kernel(const uint16_t* _
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 // |a| > sigma in fp16 == in fp32 (both operands are fp16 values); NaN compares false like torch
-                flags |= (__builtin_fabsf(h2f((uint16_t)(w[e] & 0xffffu))) > sigma ? 1u : 0u) << (2 * e);
-                flags |= (__builtin_fabsf(h2f((uint16_t)(w[e] >> 16))) > sigma ? 1u : 0u) << (2 * e + 1);
+                flags |= (__builtin_fabsf(o2f<BF>((uint16_t)(w[e] & 0xffffu))) > sigma ? 1u : 0u) << (2 * e);
+                flags |= (__builtin_fabsf(o2f<BF>((uint16_t)(w[e] >> 16))) > sigma ? 1u : 0u) << (2 * e + 1);
             }
         }
         if (flags) atomicOr(mask + (v >> 2), flags << ((v & 3) * 8));
@@ -80,6 +82,8 @@ __global__ __launch_bounds__(1024) void outlier_compact_kernel(const unsigned* _
 }
 
 // out[n, j] = fp16( fp16(W[n, ind[j]]) * sW[n] ): one thread per element, rows of `out` contiguous.
+// BF: out is bf16 (sW stays fp16): bf16(fp32(W) * fp32(sW)), the exact fp32 product rounded once.  An ind[j] outside [0, K) gives a zero column.
+template <bool BF>
 __global__ __launch_bounds__(OBLOCK) void dequant_columns_kernel(const int8_t* __restrict__ W,
                                                                  const uint16_t* __restrict__ sW,
                                                                  const int32_t* __restrict__ ind, int len,
@@ -90,12 +94,13 @@ __global__ __launch_bounds__(OBLOCK) void dequant_columns_kernel(const int8_t* _
         const int n = (int)(i / len), j = (int)(i - (int64_t)n * len);
         const int c = ind[j];
         const float w = (c >= 0 && c < K) ? (float)W[(int64_t)n * K + c] : 0.f;
-        out[i] = f2h_bits(w * h2f(sW[n])); // int8 is exact in fp16; one rounding of the exact product
+        if constexpr (BF) out[i] = (c >= 0 && c < K) ? f2bf_bits(w * h2f(sW[n])) : (uint16_t)0; // (0 x inf scale would be NaN: the padding column is +0)
+        else out[i] = f2h_bits(w * h2f(sW[n])); // int8 is exact in fp16; one rounding of the exact product
     }
 }
 
 hipError_t launch_find_outliers(const void* A, int M, int K, float sigma, unsigned* mask, int32_t* ind, int32_t* count,
-                                int capacity, hipStream_t st)
+                                int capacity, hipStream_t st, bool bf16)
 {
     const int words = (K + 31) / 32;
     hipError_t e = hipMemsetAsync(mask, 0, (size_t)words * 4, st);
@@ -107,21 +112,30 @@ hipError_t launch_find_outliers(const void* A, int M, int K, float sigma, unsign
         int rows_per_block = (int)(((int64_t)M * gx + 4095) / 4096);
         if (rows_per_block < 8) rows_per_block = 8;
         const int gy = (M + rows_per_block - 1) / rows_per_block;
-        hipLaunchKernelGGL(outlier_flags_kernel, dim3((unsigned)gx, (unsigned)gy), dim3(OBLOCK), 0, st,
-                           static_cast<const uint16_t*>(A), mask, M, K, sigma, rows_per_block);
+        if (bf16)
+            hipLaunchKernelGGL(outlier_flags_kernel<true>, dim3((unsigned)gx, (unsigned)gy), dim3(OBLOCK), 0, st,
+                               static_cast<const uint16_t*>(A), mask, M, K, sigma, rows_per_block);
+        else
+            hipLaunchKernelGGL(outlier_flags_kernel<false>, dim3((unsigned)gx, (unsigned)gy), dim3(OBLOCK), 0, st,
+                               static_cast<const uint16_t*>(A), mask, M, K, sigma, rows_per_block);
     }
     hipLaunchKernelGGL(outlier_compact_kernel, dim3(1), dim3(1024), 0, st, mask, K, ind, count, capacity);
     return hipGetLastError();
 }
 
 hipError_t launch_dequant_columns(const int8_t* W, const void* sW, const int32_t* ind, int len, void* out, int N, int K,
-                                  hipStream_t st)
+                                  hipStream_t st, bool bf16)
 {
     if (N <= 0 || len <= 0) return hipSuccess;
     const int64_t total = (int64_t)N * len;
     const int64_t want = (total + OBLOCK - 1) / OBLOCK;
-    hipLaunchKernelGGL(dequant_columns_kernel, dim3((unsigned)(want < 8192 ? want : 8192)), dim3(OBLOCK), 0, st, W,
-                       static_cast<const uint16_t*>(sW), ind, len, static_cast<uint16_t*>(out), N, K);
+    const dim3 grid((unsigned)(want < 8192 ? want : 8192));
+    if (bf16)
+        hipLaunchKernelGGL(dequant_columns_kernel<true>, grid, dim3(OBLOCK), 0, st, W, static_cast<const uint16_t*>(sW), ind, len,
+                           static_cast<uint16_t*>(out), N, K);
+    else
+        hipLaunchKernelGGL(dequant_columns_kernel<false>, grid, dim3(OBLOCK), 0, st, W, static_cast<const uint16_t*>(sW), ind, len,
+                           static_cast<uint16_t*>(out), N, K);
     return hipGetLastError();
 }
 

@@ -26,16 +26,16 @@ constexpr int QBLOCK = 256;
 // bytes 4 KiB apart (gemm_skinny_kernels.hip; 32 x 4096 x 4096: GEMM 7.9 -> 5.4 us).
 // (A K-slice-major image [K / 128][M][128 B] for the 256 x 256 ping-pong GEMM was FRAG == 2 for one build: GEMM -0.3 %, this kernel
 //  +7.6 %, end to end -0.35 %: removed; the GEMM keeps its reader, ablation 512.)
-// BF (bf16 calls, ZERO == false only): A, sA and fpA are bf16; sA = bf16(fp32(amax) / 127), q = sat[-127, 127](rint(x / sA)) with the
+// BF (bf16 calls, either flavour): A, sA and fpA are bf16; sA = bf16(fp32(amax) / 127), q = sat[-127, 127](rint(x / sA)) with the
 // IEEE fp32 quotient (a NaN quotient gives 0) -- the fp16 rule's fp16 rounding of the quotient would move integers near 127 by up to
-// 0.5 in bf16.
+// 0.5 in bf16.  ZERO: amax and q are taken from the ZEROED row (the P flavour: mixq_quant_extract_typed, mixq_mixlinear_forward_typed).
+// An ind[j] outside [0, K) gathers +0 and zeroes nothing (bf16 forms only: the padding of a bf16 P-flavour outlier set is -1).
 template <int TPR, int MAXV, bool ZERO, int FRAG = 0, bool BF = false>
 __global__ __launch_bounds__(QBLOCK) void quant_extract_kernel(uint16_t* __restrict__ A, int8_t* __restrict__ qA,
                                                                uint16_t* __restrict__ sA, uint16_t* __restrict__ fpA,
                                                                const int32_t* __restrict__ ind, int M, int K, int O,
                                                                unsigned* __restrict__ zero_words, void* dbg)
 {
-    static_assert(!(BF && ZERO), "the bf16 producer is the T flavour (A untouched)");
     constexpr int INF_BITS = BF ? 0x7f80 : 0x7c00; // |x| bit pattern of +inf: larger patterns are NaNs
     dbg_stamp(dbg, 0); // (measurement only: NULL in production) entry
     // (enqueue: the hand-over words of the GEMM's K split over workgroups are cleared here, one launch earlier, instead
@@ -73,7 +73,14 @@ __global__ __launch_bounds__(QBLOCK) void quant_extract_kernel(uint16_t* __restr
     // outlier gather (before any zero write-back); strided over the row's TPR threads
     dbg_stamp(dbg, 1); // row loads issued
     if (fpA != nullptr && row_ok) {
-        for (int j = t; j < O; j += TPR) fpA[row * (int64_t)O + j] = A[row * (int64_t)K + ind[j]];
+        if constexpr (BF) {
+            for (int j = t; j < O; j += TPR) {
+                const int c = ind[j];
+                fpA[row * (int64_t)O + j] = (c >= 0 && c < K) ? A[row * (int64_t)K + c] : (uint16_t)0;
+            }
+        } else {
+            for (int j = t; j < O; j += TPR) fpA[row * (int64_t)O + j] = A[row * (int64_t)K + ind[j]];
+        }
     }
     dbg_stamp(dbg, 2); // outlier gather issued (two dependent loads + a store per element)
 
@@ -242,7 +249,11 @@ __global__ __launch_bounds__(QBLOCK) void quant_extract_long_kernel(uint16_t* __
     }
     const uint16_t* a = A + row * (int64_t)K;
     if (fpA != nullptr)
-        for (int j = tid; j < O; j += QBLOCK) fpA[row * (int64_t)O + j] = a[ind[j]];
+        for (int j = tid; j < O; j += QBLOCK) {
+            const int c = ind[j];
+            if constexpr (BF) fpA[row * (int64_t)O + j] = (c >= 0 && c < K) ? a[c] : (uint16_t)0;
+            else fpA[row * (int64_t)O + j] = a[c];
+        }
     int amax = -1;
     for (int k = tid; k < K; k += QBLOCK) {
         int b = (ZERO && ((reinterpret_cast<const unsigned*>(zmask)[k >> 5] >> (k & 31)) & 1u)) ? 0 : (a[k] & 0x7fff);
@@ -259,7 +270,7 @@ __global__ __launch_bounds__(QBLOCK) void quant_extract_long_kernel(uint16_t* __
     if (tid == 0) sA[row] = s_bits;
     for (int k = tid; k < K; k += QBLOCK) {
         bool z = ZERO && ((reinterpret_cast<const unsigned*>(zmask)[k >> 5] >> (k & 31)) & 1u);
-        if constexpr (BF) qA[row * (int64_t)K + k] = (int8_t)quant_one_bf16(bf2f(a[k]), s);
+        if constexpr (BF) qA[row * (int64_t)K + k] = (int8_t)quant_one_bf16(z ? 0.f : bf2f(a[k]), s);
         else qA[row * (int64_t)K + k] = (int8_t)quant_one(z ? 0.f : h2f(a[k]), s);
     }
     if (ZERO) {
@@ -345,33 +356,34 @@ static void note_qe(bool nt)
     note_producer_kernel(n[nt ? 1 : 0].c_str());
 }
 
-// the bf16 producer's name: the fp16 form's name + " [bf16]"
-template <int TPR, int MAXV, int FRAG>
+// the bf16 producer's name: the fp16 form's name + " [bf16]", " nt" behind it
+template <int TPR, int MAXV, bool ZERO, int FRAG>
 static void note_qe_bf16(bool nt)
 {
-    static const std::string n[2] = {producer_form_name("quant_extract_kernel", TPR, MAXV, "ZERO", 0, FRAG, false) + " [bf16]",
-                                     producer_form_name("quant_extract_kernel", TPR, MAXV, "ZERO", 0, FRAG, true) + " [bf16]"};
+    static const std::string n[2] = {producer_form_name("quant_extract_kernel", TPR, MAXV, "ZERO", ZERO, FRAG, false) + " [bf16]",
+                                     producer_form_name("quant_extract_kernel", TPR, MAXV, "ZERO", ZERO, FRAG, false) + " [bf16] nt"};
     note_producer_kernel(n[nt ? 1 : 0].c_str());
 }
 
-// bf16 calls: the same grid, the same forms, quant_extract_bf16_kernel
-template <int TPR, int MAXV>
+// bf16 calls: the same grid, the same forms, the same dynamic LDS mask (ZERO), the BF instantiations
+template <int TPR, int MAXV, bool ZERO>
 static hipError_t launch_qe_bf16(uint16_t* A, int8_t* qA, uint16_t* sA, uint16_t* fpA, const int32_t* ind, int M, int K, int O,
                                  hipStream_t st, unsigned* zw, int frag)
 {
     void* const dbg = g_quant_stamps.load(std::memory_order_relaxed);
+    const size_t sm = ZERO ? (size_t)((K + 31) / 32) * 4 : 0;
     if constexpr (TPR == 256 && MAXV <= 8) {
         if (frag == 1) {
-            note_qe_bf16<TPR, MAXV, 1>(false);
-            hipLaunchKernelGGL((quant_extract_kernel<TPR, MAXV, false, 1, true>), dim3((unsigned)M), dim3(QBLOCK), 0, st, A, qA, sA, fpA, ind, M, K,
+            note_qe_bf16<TPR, MAXV, ZERO, 1>(false);
+            hipLaunchKernelGGL((quant_extract_kernel<TPR, MAXV, ZERO, 1, true>), dim3((unsigned)M), dim3(QBLOCK), sm, st, A, qA, sA, fpA, ind, M, K,
                                O, zw, dbg);
             return hipGetLastError();
         }
     }
     if (frag != 0) return hipErrorInvalidValue;
     constexpr int RPB = QBLOCK / TPR;
-    note_qe_bf16<TPR, MAXV, 0>((int64_t)M * K >= ((int64_t)8 << 20));
-    hipLaunchKernelGGL((quant_extract_kernel<TPR, MAXV, false, 0, true>), dim3((unsigned)((M + RPB - 1) / RPB)), dim3(QBLOCK), 0, st, A, qA, sA,
+    note_qe_bf16<TPR, MAXV, ZERO, 0>((int64_t)M * K >= ((int64_t)8 << 20));
+    hipLaunchKernelGGL((quant_extract_kernel<TPR, MAXV, ZERO, 0, true>), dim3((unsigned)((M + RPB - 1) / RPB)), dim3(QBLOCK), sm, st, A, qA, sA,
                        fpA, ind, M, K, O, zw, dbg);
     return hipGetLastError();
 }
@@ -380,7 +392,9 @@ template <int TPR, int MAXV>
 static hipError_t launch_qe(uint16_t* A, int8_t* qA, uint16_t* sA, uint16_t* fpA, const int32_t* ind, int M, int K,
                             int O, bool zero, hipStream_t st, unsigned* zw, int frag = 0, bool bf16 = false)
 {
-    if (bf16) return launch_qe_bf16<TPR, MAXV>(A, qA, sA, fpA, ind, M, K, O, st, zw, frag);
+    if (bf16)
+        return zero ? launch_qe_bf16<TPR, MAXV, true>(A, qA, sA, fpA, ind, M, K, O, st, zw, frag)
+                    : launch_qe_bf16<TPR, MAXV, false>(A, qA, sA, fpA, ind, M, K, O, st, zw, frag);
     void* const dbg = g_quant_stamps.load(std::memory_order_relaxed);
     if constexpr (TPR == 256 && MAXV <= 8) {
         if (frag == 1) { // decode batches: qA in the skinny GEMM's fragment order (both flavours)
@@ -431,7 +445,6 @@ bool quant_frag_layout_supported(int M, int K) { return M > 0 && M <= 64 && K % 
 hipError_t launch_quant_extract(void* A, int8_t* qA, void* sA, void* fpA, const int32_t* ind, int M, int K, int O,
                                 bool zero, hipStream_t st, void* zero_words, int frag, bool bf16)
 {
-    if (bf16 && zero) return hipErrorInvalidValue; // (the bf16 producer is the T flavour)
     if (frag == 1 && !quant_frag_layout_supported(M, K)) return hipErrorInvalidValue;
     if (frag < 0 || frag > 1) return hipErrorInvalidValue;
     if (M <= 0) return hipSuccess;
@@ -453,7 +466,11 @@ hipError_t launch_quant_extract(void* A, int8_t* qA, void* sA, void* fpA, const 
     if (nvec <= 256 * 8) return launch_qe<256, 8>(a, qA, s, f, ind, M, K, O, zero, st, zw, frag, bf16);
     if (nvec <= 256 * 16) return launch_qe<256, 16>(a, qA, s, f, ind, M, K, O, zero, st, zw, frag, bf16);
     dim3 grid((unsigned)M), block(QBLOCK);
-    if (bf16) {
+    if (bf16 && zero) {
+        note_producer_kernel("quant_extract_long_kernel<ZERO=1> [bf16]");
+        size_t sm = (size_t)((K + 31) / 32) * 4;
+        hipLaunchKernelGGL((quant_extract_long_kernel<true, true>), grid, block, sm, st, a, qA, s, f, ind, M, K, O, zw);
+    } else if (bf16) {
         note_producer_kernel("quant_extract_long_kernel<ZERO=0> [bf16]");
         hipLaunchKernelGGL((quant_extract_long_kernel<false, true>), grid, block, 0, st, a, qA, s, f, ind, M, K, O, zw);
     } else if (zero) {

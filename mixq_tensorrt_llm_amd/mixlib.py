@@ -132,11 +132,37 @@ def _dev(*ts):
         assert t.is_contiguous(), "mixlib ops need contiguous tensors"
 
 
+def _p_dtype(what, x, **operands):
+    """The activation type of a P-flavour op: ``x``'s, fp16 or bf16 (MI355X extension).  The named operands (row scales, outliers,
+    outlier weights, outputs) must have it: a mixed call raises ``TypeError`` before anything reaches the library, which sees raw
+    pointers only."""
+    dt = x.dtype
+    if dt not in (torch.float16, torch.bfloat16):
+        raise TypeError(f"{what}: the activation is {dt}; fp16 and bf16 are supported")
+    for name, t in operands.items():
+        if t is not None and t.dtype != dt:
+            raise TypeError(f"{what}: {name} is {t.dtype} in a {'bf16' if dt == torch.bfloat16 else 'fp16'} call")
+    return dt
+
+
+def _type_code(dt):
+    return _lib.MIXQ_TYPE_BF16 if dt == torch.bfloat16 else _lib.MIXQ_TYPE_HALF
+
+
 @_on_tensor_device
 def FindRowScale(x, scaleRow, rows, cols, bit=8):
-    """cult.cu:2569-2608.  Writes the per-row fp16 scale into ``scaleRow`` and returns the int8 rows."""
+    """cult.cu:2569-2608.  Writes the per-row scale into ``scaleRow`` and returns the int8 rows.  fp16, or (MI355X extension,
+    ``mixq_quant_extract_typed``, bit 8 only) bf16 ``x`` / ``scaleRow``: scale = bf16(amax / 127), q = sat(rint(x / scale))."""
+    dt = _p_dtype("FindRowScale", x, scaleRow=scaleRow)
+    if dt == torch.bfloat16 and bit != 8:
+        raise TypeError("FindRowScale: there is no bf16 form of the packed 4-bit quantiser (bf16 rows take bit = 8)")
     _dev(x, scaleRow)
     _rows_fit(scaleRow, rows, "FindRowScale")
+    if dt == torch.bfloat16:
+        out = torch.empty((rows, cols), dtype=torch.int8, device=x.device)
+        _lib.check(_lib.load().mixq_quant_extract_typed(rows, cols, _p(x), _p(out), _p(scaleRow), None, None, 0, 0, QA_ROW_MAJOR,
+                                                        _lib.MIXQ_TYPE_BF16, _st(x)), "FindRowScale")
+        return out
     if bit == 4:  # cult.cu:2588-2606: packed int4 pairs, scale = amax / 7
         assert cols % 2 == 0
         out = torch.empty((rows, cols // 2), dtype=torch.uint8, device=x.device)
@@ -150,12 +176,14 @@ def FindRowScale(x, scaleRow, rows, cols, bit=8):
 
 @_on_tensor_device
 def ExtractOutliersAndSetToZeros(ind, input):
-    """cult.cu:1433-1465.  Returns input[:, ind] (fp16 [M, len]) and ZEROES those columns of ``input`` in place."""
+    """cult.cu:1433-1465.  Returns input[:, ind] ([M, len] of ``input``'s type, fp16 or bf16: a bit copy) and ZEROES those columns of
+    ``input`` in place.  Every index lies in [0, K)."""
+    dt = _p_dtype("ExtractOutliersAndSetToZeros", input)
     _dev(ind, input)
-    assert ind.dtype == torch.int32 and input.dtype == torch.float16
+    assert ind.dtype == torch.int32
     m, k = input.shape
     n = ind.shape[0]
-    out = torch.empty((m, n), dtype=torch.float16, device=input.device)  # (every element is written: no memset launch)
+    out = torch.empty((m, n), dtype=dt, device=input.device)  # (every element is written: no memset launch)
     _lib.check(_lib.load().mixq_extract_outliers_set_zero(m, k, _p(input), _p(out), _p(ind), n, _st(input)),
                "ExtractOutliersAndSetToZeros")
     return out
@@ -355,12 +383,20 @@ def Int8quantize(src, scale):
 
 @_on_tensor_device
 def FindRowScaleFusedExtracOutliers(x, scaleRow, ind, len_ind, rows, cols, q_layout=0):
-    """cult.cu:2671-2709: returns [int8 rows, outliers fp16 [rows,len_ind]]; zeroes the outlier columns of x.
-    ``q_layout`` (MI355X extension): write the rows in the consumer's preferred image (``qa_layout()``)."""
+    """cult.cu:2671-2709: returns [int8 rows, outliers [rows,len_ind]]; zeroes the outlier columns of x.
+    ``q_layout`` (MI355X extension): write the rows in the consumer's preferred image (``qa_layout()``).
+    fp16, or (MI355X extension, ``mixq_quant_extract_typed``) bf16 ``x`` / ``scaleRow`` with bf16 outliers: the bf16 quantiser on the
+    zeroed row; an index of -1 (the padding of a bf16 outlier set) gives a zero outlier column and zeroes nothing."""
+    dt = _p_dtype("FindRowScaleFusedExtracOutliers", x, scaleRow=scaleRow)
     _dev(x, scaleRow)
     _rows_fit(scaleRow, rows, "FindRowScaleFusedExtracOutliers")
     q = _alloc_q(rows, cols, q_layout, x.device)
-    outl = torch.empty((rows, len_ind), dtype=torch.float16, device=x.device)
+    outl = torch.empty((rows, len_ind), dtype=dt, device=x.device)
+    if dt == torch.bfloat16:
+        _lib.check(_lib.load().mixq_quant_extract_typed(rows, cols, _p(x), _p(q), _p(scaleRow), _p(outl), _p(ind) if len_ind else None,
+                                                        len_ind, 1, q_layout, _lib.MIXQ_TYPE_BF16, _st(x)),
+                   "FindRowScaleFusedExtracOutliers")
+        return [q, outl]
     _lib.check(_lib.load().mixq_quant_extract_layout(rows, cols, _p(x), _p(q), _p(scaleRow), _p(outl),
                                                      _p(ind) if len_ind else None, len_ind, 1, q_layout, _st(x)),
                "FindRowScaleFusedExtracOutliers")
@@ -535,11 +571,13 @@ def add_layernorm_forward_cuda_extract_outliers_int4(_input, _residual, _gamma, 
 
 @_on_tensor_device
 def ExtractOutliers(ind, input):
-    """cult.cu ExtractOutliers: input[:, ind] as fp16 [M, len]; `input` is left untouched (T-flavour gather)."""
+    """cult.cu ExtractOutliers: input[:, ind] as [M, len] of ``input``'s type (fp16 or bf16: a bit copy); `input` is left untouched
+    (T-flavour gather)."""
+    dt = _p_dtype("ExtractOutliers", input)
     _dev(ind, input)
     m, k = input.shape
     n = ind.shape[0]
-    out = torch.zeros((m, n), dtype=torch.float16, device=input.device)
+    out = torch.zeros((m, n), dtype=dt, device=input.device)
     _lib.check(_lib.load().mixq_extract_outliers(m, k, _p(input), _p(out), _p(ind), n, _st(input)), "ExtractOutliers")
     return out
 
@@ -669,26 +707,37 @@ def gemm_mixed(q, W_int8, x_scale, sW, outliers, fp_weight, M, N, K, bias=None, 
 @_on_tensor_device
 def mixlinear_forward(x, ind, q_weight, scale_col, weight_cache, x_scale, q_layout=0):
     """MixLinear_GEMM.forward (linear.py:163-286, bit = 8, static outlier set) in ONE library call and two launches (MI355X
-    extension, include/mixq.h ``mixq_mixlinear_forward``): returns (out fp16 [M,N], q_x int8 [M,K], outliers fp16 [M,O]); zeroes
+    extension, include/mixq.h ``mixq_mixlinear_forward``): returns (out [M,N], q_x int8 [M,K], outliers [M,O]); zeroes
     the ``ind`` columns of ``x`` and fills ``x_scale`` like the reference's four-call sequence.  The wrapper does what one of
-    the four wrappers does -- the host cost per linear drops ~4x (profiles/r03_mixlib_overhead.txt)."""
+    the four wrappers does -- the host cost per linear drops ~4x (profiles/r03_mixlib_overhead.txt).
+    fp16, or (``mixq_mixlinear_forward_typed``) bf16 ``x`` / ``weight_cache`` / ``x_scale`` with bf16 results; ``scale_col`` stays
+    fp16.  A bf16 call takes a multiple of 8 and at most 128 outlier columns, -1 entries of ``ind`` being zero columns."""
+    dt = _p_dtype("mixlinear_forward", x, x_scale=x_scale, weight_cache=weight_cache if ind.shape[0] else None)
+    if scale_col.dtype != torch.float16:
+        raise TypeError(f"mixlinear_forward: scale_col is {scale_col.dtype}; the weight scales stay fp16 in either type")
     _dev(x, ind, q_weight, scale_col, x_scale)   # (the same guards as the four wrappers this call replaces: raw pointers go to C)
     if weight_cache is not None:
         _dev(weight_cache)
-    assert x.dtype == torch.float16 and ind.dtype == torch.int32 and q_weight.dtype == torch.int8
-    assert scale_col.dtype == torch.float16 and x_scale.dtype == torch.float16
+    assert ind.dtype == torch.int32 and q_weight.dtype == torch.int8
     M, K = x.shape
     N = q_weight.shape[0]
     O = int(ind.shape[0])
     assert q_weight.shape[1] == K and scale_col.numel() >= N, "mixlinear_forward: q_weight [N,K] / scale_col [N] do not match x [M,K]"
-    assert weight_cache is None or O == 0 or (weight_cache.dtype == torch.float16 and weight_cache.numel() >= N * O)
+    assert weight_cache is None or O == 0 or weight_cache.numel() >= N * O
     _rows_fit(x_scale, M, "mixlinear_forward")
     dev = x.device
-    out = torch.empty((M, N), dtype=torch.float16, device=dev)
+    out = torch.empty((M, N), dtype=dt, device=dev)
     q_x = _alloc_q(M, K, q_layout, dev)   # (q_layout = qa_layout(M, N, K): the opaque fragment-major image for decode batches)
-    outliers = torch.empty((M, O), dtype=torch.float16, device=dev)
+    outliers = torch.empty((M, O), dtype=dt, device=dev)
     lib = _lib.load()
     scratch = None if q_layout else gemm_scratch(x, M, N, K)
+    if dt == torch.bfloat16:
+        _lib.check(lib.mixq_mixlinear_forward_typed(M, N, K, O, x.data_ptr(), ind.data_ptr() if O else None, q_weight.data_ptr(),
+                                                    scale_col.data_ptr(), weight_cache.data_ptr() if (O and weight_cache is not None) else None,
+                                                    x_scale.data_ptr(), q_x.data_ptr(), outliers.data_ptr() if O else None, out.data_ptr(),
+                                                    q_layout, _lib.MIXQ_TYPE_BF16, scratch.data_ptr() if scratch is not None else None,
+                                                    scratch.numel() if scratch is not None else 0, _st(x)), "mixlinear_forward")
+        return out, q_x, outliers
     _lib.check(lib.mixq_mixlinear_forward(M, N, K, O, x.data_ptr(), ind.data_ptr() if O else None, q_weight.data_ptr(),
                                           scale_col.data_ptr(), weight_cache.data_ptr() if (O and weight_cache is not None) else None,
                                           x_scale.data_ptr(),

@@ -12,6 +12,10 @@ path): FindOutliers -> `mixq_find_outliers`, weight_cache columns -> `mixq_dequa
 -> `mixq_gemm_fp16`, the rest are the mixlib ops.  torch is used for allocation, `hstack` of the growing state and the
 quantize-time `from_linear` (like the reference).  bit = 8 and bit = 4 (W4A4: packed int4 storage, sign-extended to
 int8 for the MFMA kernels -- gfx950 has no int4 matrix instruction) and the weight-only W8A16 mode.
+
+bf16 (MI355X extension): ``MixLinear_GEMM(dtype=torch.bfloat16)`` (bit = 8) runs the same state machine on bf16 rows -- the typed
+entries `mixq_quant_extract_typed`, `mixq_find_outliers_typed`, `mixq_dequant_weight_columns_typed`, `mixq_mixlinear_forward_typed` --
+with the outlier product inside the fused GEMM and a set padded with -1 to a multiple of 8, at most 128 columns.
 """
 import ctypes
 
@@ -24,8 +28,10 @@ from .mixlib import _p, _st  # noqa: E402  (raw pointers / the raw current strea
 
 
 def find_outliers(activation: torch.Tensor, sigma: float, capacity: int = None) -> torch.Tensor:
-    """linear.py:155-161 ``torch.unique(torch.where(A.abs() > sigma)[1]).to(int32)``: ascending column indices."""
-    assert activation.is_cuda and activation.dtype == torch.float16 and activation.dim() == 2
+    """linear.py:155-161 ``torch.unique(torch.where(A.abs() > sigma)[1]).to(int32)``: ascending column indices.
+    fp16 or (MI355X extension, ``mixq_find_outliers_typed``) bf16 rows, compared in fp32 as torch does against an fp16 sigma."""
+    dt = mixlib._p_dtype("find_outliers", activation)
+    assert activation.is_cuda and activation.dim() == 2
     a = activation.contiguous()
     m, k = a.shape
     cap = k if capacity is None else capacity
@@ -33,20 +39,42 @@ def find_outliers(activation: torch.Tensor, sigma: float, capacity: int = None) 
     ws = torch.empty((lib.mixq_find_outliers_workspace_size(k) + 3) // 4, dtype=torch.int32, device=a.device)
     ind = torch.empty(cap, dtype=torch.int32, device=a.device)
     cnt = torch.zeros(1, dtype=torch.int32, device=a.device)
-    _lib.check(lib.mixq_find_outliers(_p(a), m, k, ctypes.c_float(float(sigma)), _p(ws), _p(ind), _p(cnt), cap, _st(a)),
-               "find_outliers")
+    if dt == torch.bfloat16:
+        _lib.check(lib.mixq_find_outliers_typed(_p(a), m, k, ctypes.c_float(float(sigma)), _p(ws), _p(ind), _p(cnt), cap,
+                                                _lib.MIXQ_TYPE_BF16, _st(a)), "find_outliers")
+    else:
+        _lib.check(lib.mixq_find_outliers(_p(a), m, k, ctypes.c_float(float(sigma)), _p(ws), _p(ind), _p(cnt), cap, _st(a)),
+                   "find_outliers")
     n = int(cnt.item())  # the reference's torch.unique synchronises too (data-dependent output size)
     return ind[: min(n, cap)]
 
 
-def dequant_weight_columns(q_weight: torch.Tensor, scale_col: torch.Tensor, ind: torch.Tensor) -> torch.Tensor:
-    """linear.py:207-209 ``q_weight[:, ind].to(float16) * scale_col.T`` -> fp16 [N, len(ind)]."""
+def dequant_weight_columns(q_weight: torch.Tensor, scale_col: torch.Tensor, ind: torch.Tensor,
+                           dtype=torch.float16) -> torch.Tensor:
+    """linear.py:207-209 ``q_weight[:, ind].to(float16) * scale_col.T`` -> fp16 [N, len(ind)].
+    ``dtype=torch.bfloat16`` (MI355X extension, ``mixq_dequant_weight_columns_typed``): bf16(fp32(q) * fp32(scale)), one rounding;
+    ``scale_col`` stays fp16; an index outside [0, K) (the -1 padding of a bf16 outlier set) gives a zero column."""
+    if dtype not in (torch.float16, torch.bfloat16):
+        raise TypeError(f"dequant_weight_columns: dtype is {dtype}; fp16 and bf16 are supported")
+    if scale_col.dtype != torch.float16:
+        raise TypeError(f"dequant_weight_columns: scale_col is {scale_col.dtype}; the weight scales stay fp16 in either type")
     assert q_weight.is_cuda and q_weight.dtype == torch.int8 and ind.dtype == torch.int32
     n, k = q_weight.shape
-    out = torch.empty((n, ind.shape[0]), dtype=torch.float16, device=q_weight.device)
+    out = torch.empty((n, ind.shape[0]), dtype=dtype, device=q_weight.device)
+    if dtype == torch.bfloat16:
+        _lib.check(_lib.load().mixq_dequant_weight_columns_typed(_p(q_weight), _p(scale_col), _p(ind), ind.shape[0], _p(out), n, k,
+                                                                 _lib.MIXQ_TYPE_BF16, _st(q_weight)), "dequant_weight_columns")
+        return out
     _lib.check(_lib.load().mixq_dequant_weight_columns(_p(q_weight), _p(scale_col), _p(ind), ind.shape[0], _p(out), n,
                                                        k, _st(q_weight)), "dequant_weight_columns")
     return out
+
+
+BF16_MAX_OUTLIERS = 128   # outlier columns a bf16 layer holds at most: one LDS pass of the fused GEMM (the bf16 epilogues take no addend)
+
+
+def _pad8(n):
+    return (n + 7) // 8 * 8
 
 
 def two_compl(x: torch.Tensor, bits: int) -> torch.Tensor:
@@ -72,7 +100,8 @@ def outlier_product(activation_outliers: torch.Tensor, weight_cache: torch.Tenso
 
 class MixLibCache:
     """Cache.py:5-24: per-model scratch shared by the layers (row scales, sigma, the running outlier state).
-    ``dtype=torch.bfloat16`` (MI355X extension): the row scales of a bf16 producer (``FasterTransformerRMSNorm(dtype=bf16)``)."""
+    ``dtype=torch.bfloat16`` (MI355X extension): the row scales of a bf16 producer (``FasterTransformerRMSNorm(dtype=bf16)``) and of
+    bf16 layers (``MixLinear_GEMM(dtype=bf16)``)."""
 
     def __init__(self, inputdim=1024, sigma=6, bit=8, device="cuda", dtype=torch.float16):
         assert dtype in (torch.float16, torch.bfloat16)
@@ -96,11 +125,25 @@ class MixLibCache:
 
 
 class MixLinear_GEMM:
-    """linear.py:24-286: bit = 8, bit = 4 and the weight_only W8A16 mode."""
+    """linear.py:24-286: bit = 8, bit = 4 and the weight_only W8A16 mode.
+
+    ``dtype=torch.bfloat16`` (MI355X extension; bit = 8, not weight_only, not the ``arch == 9`` route): ``weight_cache``, ``bias``,
+    inputs and outputs are bf16 (``q_weight`` / ``scale_col`` unchanged) and the cache is a ``MixLibCache(dtype=torch.bfloat16)``.
+    A bf16 layer never feeds an fp16 addend: every GEMM is ``mixlib.gemm_mixed`` with the outlier product in the kernel (or
+    ``mixlib.mixlinear_forward`` on the unfused static route).  For that ``ind``, ``weight_cache``'s columns and
+    ``cache.activation_outliers``' columns always have the same count, a multiple of 8 and at most 128: the real columns lead,
+    the padding is ``ind = -1`` with zero weight and activation columns (the bf16 producers and ``dequant_weight_columns`` define -1).
+    Dynamic growth stops at 128 real columns (fp16: beyond 256)."""
 
     def __init__(self, in_features, out_features, bias, dev, bit=8, weight_only=False, cache=None,
-                 fp_features_num=256):
+                 fp_features_num=256, dtype=torch.float16):
         assert bit in (8, 4)
+        if dtype not in (torch.float16, torch.bfloat16):
+            raise TypeError(f"MixLinear_GEMM: dtype is {dtype}; fp16 and bf16 are supported")
+        if dtype == torch.bfloat16 and (bit != 8 or weight_only):
+            raise TypeError("MixLinear_GEMM: a bf16 layer takes bit = 8 and not weight_only (there is no bf16 4-bit producer "
+                            "and no bf16 route through the weight-only GEMM here)")
+        self.dtype = dtype
         self.in_features, self.out_features, self.bit = in_features, out_features, bit
         self.fp_features_num = fp_features_num
         self.weight_only = weight_only
@@ -118,7 +161,7 @@ class MixLinear_GEMM:
                 self.q_weight = torch.empty((out_features, in_features // 2), dtype=torch.uint8, device=dev)
                 self.weight_cache = torch.empty((out_features, fp_features_num), dtype=torch.float16, device=dev)
                 self.ind = torch.empty((fp_features_num,), dtype=torch.int32, device=dev)
-        self.bias = torch.empty((out_features,), dtype=torch.float16, device=dev) if bias else None
+        self.bias = torch.empty((out_features,), dtype=dtype, device=dev) if bias else None
         self.cnt = 0
         # linear.py:86 `self.arch = torch.cuda.get_device_capability()[0]`, read at :231 / :317: 9 (sm90) takes the UNFUSED route
         # mixlib.gemm -> outlier product -> mixlib.dequantizeInt8[Silu]; everything else the fused GEMM.  An MI355X reports no CUDA
@@ -133,12 +176,13 @@ class MixLinear_GEMM:
 
     @classmethod
     def from_linear(cls, weight, bias=None, bit=8, weight_only=False, cache=None, dev="cuda", layer_scales=None,
-                    fp_features_num=256):
+                    fp_features_num=256, dtype=torch.float16):
         """linear.py:88-149 (``linear.weight`` fp16 [N,K], optional bias; ``layer_scales`` = per-input-channel
-        activation scales, needed for bit = 4 to pick the static outlier columns)."""
+        activation scales, needed for bit = 4 to pick the static outlier columns).  ``dtype=torch.bfloat16``: a bf16 layer
+        (``weight`` may be bf16: it is quantised from its fp32 values)."""
         n, k = weight.shape
         q = cls(k, n, bias is not None, dev, bit=bit, weight_only=weight_only, cache=cache,
-                fp_features_num=fp_features_num)
+                fp_features_num=fp_features_num, dtype=dtype)
         if weight_only:  # :102-106 EETQ quant_weights of W^T
             from . import pack
             qweight, scales, _ = pack.eetq_quant_weights(weight.t().contiguous())
@@ -156,6 +200,11 @@ class MixLinear_GEMM:
             w = torch.clamp(w.round(), -8, 7)
             q.q_weight.copy_(pack_to_i4(w.to(torch.int8).cpu()).to(dev))
             q.ind.copy_(ind.to(torch.int32).to(dev))
+        elif dtype == torch.bfloat16:   # the same rule on the fp32 values of the (bf16) weight
+            w = weight.to(dev).float()
+            scale = (torch.max(torch.abs(w), dim=1)[0].unsqueeze(1) / 127).to(torch.float16).reshape((1, n))
+            q.scale_col.copy_(scale)
+            q.q_weight.copy_(torch.clamp((w / q.scale_col.T.float()).round(), -127, 127).to(torch.int8))
         else:            # :113-120: scale = fp16(max|w| / 127) per row; q = round(w / scale) (no clamp)
             w = weight.to(dev)
             scale = (torch.max(torch.abs(w), dim=1)[0].unsqueeze(1) / 127).to(torch.float16).reshape((1, n))
@@ -164,7 +213,7 @@ class MixLinear_GEMM:
             tmp /= q.scale_col.T
             q.q_weight.copy_(tmp.round().to(torch.int8))
         if bias is not None:
-            q.bias.copy_(bias.to(dev).half())
+            q.bias.copy_(bias.to(dev).to(dtype))
         return q
 
     def prepare_decode_batches(self, enable=True):
@@ -197,6 +246,8 @@ class MixLinear_GEMM:
         q_xcache / x_scale / activation_outliers come through the cache from the preceding fused norm layer
         (`FasterTransformerRMSNorm` with ``next_layer`` set)."""
         cache = self.cache if cache is None else cache
+        if self.dtype == torch.bfloat16:
+            return self._forward_bf16(x, cache, unfused)
         cache.shape = x.shape[:-1] + (self.out_features,)
         inputs = x.reshape(-1, x.shape[-1])
         M = inputs.shape[0]
@@ -269,6 +320,111 @@ class MixLinear_GEMM:
 
     __call__ = forward
 
+    # ---- bf16 (MI355X extension) -------------------------------------------------------------------------------------------
+    def _check_bf16(self, x, cache, what):
+        if self.arch == 9:
+            raise TypeError(f"{what}: there is no bf16 form of the arch == 9 route (mixlib.gemm + dequantizeInt8 take an fp16 addend)")
+        if x.dtype != torch.bfloat16 or cache.x_scale.dtype != torch.bfloat16:
+            raise TypeError(f"{what}: a bf16 layer takes bf16 inputs and a MixLibCache(dtype=torch.bfloat16) "
+                            f"(got {x.dtype} inputs, {cache.x_scale.dtype} row scales)")
+
+    def _real_columns(self):
+        """Real (non-padding) outlier columns held: they lead ``ind``, the -1 padding follows.  Counted on the device once per
+        ``ind`` tensor (only while ``add_outliers`` is on)."""
+        known = getattr(self, "_real", None)
+        if known is None or known[0] is not self.ind:
+            known = self._real = (self.ind, int((self.ind >= 0).sum().item()) if self.ind.shape[0] else 0)
+        return known[1]
+
+    def _grow_bf16(self, cache, inputs, new):
+        """Adopt the columns ``new`` (ascending, real, disjoint from the held ones): extracted from and zeroed in ``inputs``, their
+        weights dequantised to bf16, and the set re-padded with -1 / zero columns to a multiple of 8."""
+        real = self._real_columns()
+        a_new = mixlib.ExtractOutliersAndSetToZeros(new, inputs)
+        w_new = dequant_weight_columns(self.q_weight, self.scale_col, new, dtype=torch.bfloat16)
+        n = real + int(new.shape[0])
+        pad = _pad8(n) - n
+        dev = inputs.device
+        parts_i, parts_a, parts_w = [new], [a_new], [w_new]
+        if real:
+            parts_i.insert(0, self.ind[:real])
+            parts_a.insert(0, cache.activation_outliers[:, :real])
+            parts_w.insert(0, self.weight_cache[:, :real])
+        if pad:
+            parts_i.append(torch.full((pad,), -1, dtype=torch.int32, device=dev))
+            parts_a.append(torch.zeros((a_new.shape[0], pad), dtype=torch.bfloat16, device=dev))
+            parts_w.append(torch.zeros((self.out_features, pad), dtype=torch.bfloat16, device=dev))
+        self.ind = torch.hstack(parts_i).contiguous()
+        cache.activation_outliers = torch.hstack(parts_a).contiguous()
+        self.weight_cache = torch.hstack(parts_w).contiguous()
+        self._real = (self.ind, n)
+
+    def _forward_bf16(self, x, cache, unfused):
+        self._check_bf16(x, cache, "MixLinear_GEMM.forward")
+        cache.shape = x.shape[:-1] + (self.out_features,)
+        inputs = x.reshape(-1, x.shape[-1])
+        M = inputs.shape[0]
+        n_out = int(self.ind.shape[0])
+        assert n_out % 8 == 0 and n_out <= BF16_MAX_OUTLIERS, "a bf16 layer holds a multiple of 8 and at most 128 outlier columns (-1 padded)"
+        assert cache.x_scale.numel() >= M
+        if unfused and not self.add_outliers and inputs.is_contiguous():   # static set: one library call, two launches
+            cache.ind = self.ind
+            cache.q_layout = mixlib.qa_layout(M, self.out_features, self.in_features)
+            y1, cache.q_xcache, cache.activation_outliers = mixlib.mixlinear_forward(
+                inputs, self.ind, self.q_weight, self.scale_col, self.weight_cache if n_out else None, cache.x_scale, cache.q_layout)
+            if self.bias is not None:
+                y1 += self.bias
+            return y1.reshape(cache.shape)
+        if unfused:   # the zeroing quantiser with the held (padded) set
+            cache.q_xcache, cache.activation_outliers = mixlib.FindRowScaleFusedExtracOutliers(
+                inputs, cache.x_scale, self.ind, n_out, M, self.in_features, 0)
+            cache.q_layout = 0
+        cache.ind = self.ind
+        if self.add_outliers:
+            real = self._real_columns()
+            if real < BF16_MAX_OUTLIERS and bool(cache.x_scale[0:M].max() > self.sigma / 127):
+                new = find_outliers(inputs, float(self.sigma[0, 0]), capacity=BF16_MAX_OUTLIERS - real)
+                if new.shape[0]:
+                    cache.new_ind = new
+                    self._grow_bf16(cache, inputs, new)
+                    cache.ind = self.ind
+                    cache.q_xcache = mixlib.FindRowScale(inputs, cache.x_scale, M, self.in_features, 8)
+                    cache.q_layout = 0
+            self.cnt += 1
+            if self.cnt >= cache.stop or self._real_columns() >= BF16_MAX_OUTLIERS:
+                self.add_outliers = False
+        q, lay = self._cached_q(cache, M)
+        n_out = int(self.ind.shape[0])
+        y1 = mixlib.gemm_mixed(q, self.q_weight, cache.x_scale, self.scale_col, cache.activation_outliers if n_out else None,
+                               self.weight_cache if n_out else None, M, self.out_features, self.in_features, bias=self.bias,
+                               qa_layout=lay)
+        return y1.reshape(cache.shape)
+
+    def _gate_bf16(self, x, cache, mul):
+        """``forward_without_preconditionFusedSilu`` of a bf16 layer: ONE launch, ``mul`` in its epilogue (no bias) -- the outlier
+        product runs inside the kernel.  The up projection's set is adopted whenever ``cache.ind`` is another tensor than the one
+        held: its weight columns (padding included: zero) come from the bf16 ``dequant_weight_columns``."""
+        self._check_bf16(x, cache, "MixLinear_GEMM.forward_without_preconditionFusedSilu")
+        inputs = x.reshape(-1, x.shape[-1])
+        M = inputs.shape[0]
+        if cache.ind is not self.ind:
+            self.ind = cache.ind
+            self.weight_cache = (dequant_weight_columns(self.q_weight, self.scale_col, self.ind, dtype=torch.bfloat16)
+                                 if self.ind.shape[0] else None)
+            self.forward_without_precondition_len = self.ind.shape[0]
+        n_out = int(self.ind.shape[0])
+        q, lay = self._cached_q(cache, M)
+        fused_mul = mul is not None and self.bias is None
+        y1 = mixlib.gemm_mixed(q, self.q_weight, cache.x_scale, self.scale_col, cache.activation_outliers if n_out else None,
+                               self.weight_cache if n_out else None, M, self.out_features, self.in_features, qa_layout=lay, act="silu",
+                               mul=mul.reshape(M, self.out_features) if fused_mul else None)
+        if self.bias is not None:
+            y1 += self.bias
+        y1 = y1.reshape(cache.shape)
+        if mul is not None and not fused_mul:
+            y1 *= mul
+        return y1
+
     def _row_major_q(self, cache, M):
         """q_xcache as the reference's unfused route reads it (row-major int8 [M, K])."""
         if getattr(cache, "q_layout", 0):
@@ -302,6 +458,8 @@ class MixLinear_GEMM:
         outlier columns the up projection may have added, and applies SiLU in the GEMM epilogue.  ``mul`` (MI355X
         extension, bit = 8): a [.., N] fp16 tensor multiplied into the rounded result inside the same epilogue --
         `gate *= up` without another pass over [M, N]."""
+        if self.dtype == torch.bfloat16:
+            return self._gate_bf16(x, cache, mul)
         inputs = x.reshape(-1, x.shape[-1])
         M = inputs.shape[0]
         if self.forward_without_precondition_len != cache.ind.shape[0]:
@@ -352,7 +510,8 @@ class FasterTransformerRMSNorm:
 
     ``dtype=torch.bfloat16`` (MI355X extension): a bf16 norm -- bf16 hidden state, gamma, outliers and row scales (the cache's
     ``x_scale`` must be bf16: ``MixLibCache(dtype=torch.bfloat16)``) -- in front of a layer with ``bit == 8`` that consumes the
-    cache in bf16 (``plugin.MixQLinear(dtype=torch.bfloat16).forward_quantised``).  There is no bf16 4-bit producer."""
+    cache in bf16 (``MixLinear_GEMM(dtype=torch.bfloat16)``, ``plugin.MixQLinear(dtype=torch.bfloat16).forward_quantised``).  There is
+    no bf16 4-bit producer."""
 
     def __init__(self, weight, eps=1e-6, cache=None, dtype=torch.float16):
         assert dtype in (torch.float16, torch.bfloat16)
@@ -415,7 +574,8 @@ class FasterTransformerRMSNorm:
 
 class MixLlamaMLP:
     """MixQ/src/mixquant/modules/fused/mlp.py:37-68: down(silu(gate(x)) * up(x)) where the gate projection re-uses the
-    up projection's quantised activation and has SiLU fused into its GEMM epilogue."""
+    up projection's quantised activation and has SiLU fused into its GEMM epilogue.  fp16 layers, or three bf16 layers
+    (``MixLinear_GEMM(dtype=torch.bfloat16)``) behind a bf16 ``FasterTransformerRMSNorm``."""
 
     def __init__(self, gate_proj, down_proj, up_proj, MixGemmCache=None):
         self.down_proj_, self.gate_proj_, self.up_proj_ = down_proj, gate_proj, up_proj
