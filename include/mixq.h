@@ -279,6 +279,8 @@ MIXQ_API int mixq_quant_extract_layout(int M, int K, void* A_f16, int8_t* qA, vo
 MIXQ_API int mixq_rmsnorm_extract_quant_layout(int M, int K, const void* x_f16, const void* gamma_f16, void* out_f16, float eps,
                                                const int32_t* ind, int len, void* outliers_f16, int8_t* q, void* scale_f16,
                                                int q_layout, void* stream);
+/* (An empty call, M == 0, with MIXQ_QA_FRAGMENT_MAJOR: mixq_rmsnorm_extract_quant_layout answers MIXQ_E_SHAPE; its add form below and the
+ *  typed entry on bf16 rows answer MIXQ_OK.  Kept as the entries shipped: DESIGN.md "C ABI: entries and cores".) */
 /* ---- the residual add in front of the norm, in the norm's pass (MI355X extension) --------------------------------------------
  * A decoder block adds the residual right in front of every norm (MixQ/src/mixquant/modules/fused/block.py:32-33).  Each entry below
  * is the named entry above run on h = x + residual, with h written to h_f16 -- one launch and one pass over [M, K] instead of two:

@@ -418,13 +418,57 @@ size_t mixq_reference_workspace_size(int64_t maxM, int64_t N, int64_t K)
 }
 
 // ---------------------------------------------------------------------------------------- launchers ----
+// The argument contract of each operation is written ONCE, in a core that takes a plain struct; the exported entries -- named fp16
+// forms and typed forms alike -- fill the struct and call it (DESIGN.md "C ABI: entries and cores").  A core checks by class, in this
+// order: argument values (MIXQ_E_BADARG), shapes (MIXQ_E_SHAPE), alignment (MIXQ_E_ALIGN); then an empty problem is MIXQ_OK.
+static bool type_ok(int type) { return type == MIXQ_TYPE_HALF || type == MIXQ_TYPE_BF16; }
+static bool layout_ok(int layout) { return layout == MIXQ_QA_ROW_MAJOR || layout == MIXQ_QA_FRAGMENT_MAJOR; }
+static bool misaligned(const void* p, uintptr_t bytes) { return (reinterpret_cast<uintptr_t>(p) & (bytes - 1)) != 0; }
+
+// ---- row quantiser: qA = int8 rows of A, sA their scales (+ the outlier columns gathered into fpA, and zeroed in A on request) ----
+struct QuantCall {
+    int M, K, len, q_layout;     // q_layout: MIXQ_QA_*
+    void *A, *sA, *fpA, *stream; // fpA [M, len] with ind: both unused when len == 0
+    int8_t* qA;
+    const int32_t* ind;
+    bool zero_outliers, bf16;    // bf16: A, sA, fpA are bf16
+};
+
+static int quant_entry(const QuantCall& c)
+{
+    const bool frag = c.q_layout == MIXQ_QA_FRAGMENT_MAJOR;
+    if (!layout_ok(c.q_layout)) return MIXQ_E_BADARG;
+    if (c.M < 0 || c.K <= 0 || c.len < 0 || (c.M > 0 && (!c.A || !c.qA || !c.sA))) return MIXQ_E_BADARG;
+    if (c.len > 0 && (!c.fpA || !c.ind)) return MIXQ_E_BADARG;
+    if (c.K % 8 || (frag && !mixq::quant_frag_layout_supported(c.M, c.K))) return MIXQ_E_SHAPE; // (the image of no rows is refused too)
+    if (!aligned16(c.A) || misaligned(c.qA, frag ? 16 : 8)) return MIXQ_E_ALIGN;
+    if (c.M == 0) return MIXQ_OK;
+    return hip_rc(mixq::launch_quant_extract(c.A, c.qA, c.sA, c.len > 0 ? c.fpA : nullptr, c.ind, c.M, c.K, c.len, c.zero_outliers,
+                                             static_cast<hipStream_t>(c.stream), nullptr, frag ? 1 : 0, c.bf16));
+}
+
+int mixq_quant_extract_typed(int M, int K, void* A, int8_t* qA, void* sA, void* fpA, const int32_t* ind, int len, int zero_outliers,
+                             int q_layout, int type, void* stream)
+{
+    if (!type_ok(type)) return MIXQ_E_TYPE;
+    QuantCall c{};
+    c.M = M, c.K = K, c.A = A, c.qA = qA, c.sA = sA, c.fpA = fpA, c.ind = ind, c.len = len, c.zero_outliers = zero_outliers != 0;
+    c.q_layout = q_layout, c.bf16 = type == MIXQ_TYPE_BF16, c.stream = stream;
+    return quant_entry(c);
+}
+// the named fp16 forms: the typed entry with fewer operands
+int mixq_quant_extract_layout(int M, int K, void* A, int8_t* qA, void* sA, void* fpA, const int32_t* ind, int len, int zero_outliers,
+                              int q_layout, void* stream)
+{
+    return mixq_quant_extract_typed(M, K, A, qA, sA, fpA, ind, len, zero_outliers, q_layout, MIXQ_TYPE_HALF, stream);
+}
+int mixq_quant_extract(int M, int K, void* A, int8_t* qA, void* sA, void* fpA, const int32_t* ind, int len, int zero_outliers, void* stream)
+{
+    return mixq_quant_extract_layout(M, K, A, qA, sA, fpA, ind, len, zero_outliers, MIXQ_QA_ROW_MAJOR, stream);
+}
 int mixq_int8quant(int rows, int cols, const void* src, int8_t* output, void* scale, void* stream)
 {
-    if (rows < 0 || cols <= 0 || (rows > 0 && (!src || !output || !scale))) return MIXQ_E_BADARG;
-    if (cols % 8) return MIXQ_E_SHAPE;
-    if (!aligned16(src) || (reinterpret_cast<uintptr_t>(output) & 7u)) return MIXQ_E_ALIGN;
-    return hip_rc(mixq::launch_quant_extract(const_cast<void*>(src), output, scale, nullptr, nullptr, rows, cols, 0,
-                                             false, static_cast<hipStream_t>(stream)));
+    return mixq_quant_extract(rows, cols, const_cast<void*>(src), output, scale, nullptr, nullptr, 0, 0, stream);
 }
 
 int mixq_extract_outliers(int M, int K, const void* A, void* fpA, const int32_t* ind, int len, void* stream)
@@ -442,35 +486,38 @@ int mixq_extract_outliers_set_zero(int M, int K, void* A, void* fpA, const int32
 
 size_t mixq_find_outliers_workspace_size(int K) { return K > 0 ? (size_t)((K + 31) / 32) * 4 : 0; }
 
-int mixq_find_outliers(const void* A, int M, int K, float sigma, void* mask_ws, int32_t* ind_out, int32_t* count_out,
-                       int capacity, void* stream)
+int mixq_find_outliers_typed(const void* A, int M, int K, float sigma, void* mask_ws, int32_t* ind_out, int32_t* count_out, int capacity,
+                             int type, void* stream)
 {
+    if (!type_ok(type)) return MIXQ_E_TYPE;
     if (M < 0 || K <= 0 || capacity < 0 || !mask_ws || !count_out || (capacity > 0 && !ind_out) || (M > 0 && !A))
         return MIXQ_E_BADARG;
     if (K % 8) return MIXQ_E_SHAPE;
     if (M > 0 && !aligned16(A)) return MIXQ_E_ALIGN;
-    return hip_rc(mixq::launch_find_outliers(A, M, K, sigma, static_cast<unsigned*>(mask_ws), ind_out, count_out,
-                                             capacity, static_cast<hipStream_t>(stream)));
+    return hip_rc(mixq::launch_find_outliers(A, M, K, sigma, static_cast<unsigned*>(mask_ws), ind_out, count_out, capacity,
+                                             static_cast<hipStream_t>(stream), type == MIXQ_TYPE_BF16));
+}
+
+int mixq_find_outliers(const void* A, int M, int K, float sigma, void* mask_ws, int32_t* ind_out, int32_t* count_out,
+                       int capacity, void* stream)
+{
+    return mixq_find_outliers_typed(A, M, K, sigma, mask_ws, ind_out, count_out, capacity, MIXQ_TYPE_HALF, stream);
+}
+
+int mixq_dequant_weight_columns_typed(const int8_t* q_weight, const void* scale_col, const int32_t* ind, int len, void* out, int N, int K,
+                                      int type, void* stream)
+{
+    if (!type_ok(type)) return MIXQ_E_TYPE;
+    if (N < 0 || K <= 0 || len < 0 || (N > 0 && len > 0 && (!q_weight || !scale_col || !ind || !out)))
+        return MIXQ_E_BADARG;
+    return hip_rc(mixq::launch_dequant_columns(q_weight, scale_col, ind, len, out, N, K, static_cast<hipStream_t>(stream),
+                                               type == MIXQ_TYPE_BF16));
 }
 
 int mixq_dequant_weight_columns(const int8_t* q_weight, const void* scale_col, const int32_t* ind, int len, void* out,
                                 int N, int K, void* stream)
 {
-    if (N < 0 || K <= 0 || len < 0 || (N > 0 && len > 0 && (!q_weight || !scale_col || !ind || !out)))
-        return MIXQ_E_BADARG;
-    return hip_rc(mixq::launch_dequant_columns(q_weight, scale_col, ind, len, out, N, K,
-                                               static_cast<hipStream_t>(stream)));
-}
-
-int mixq_quant_extract(int M, int K, void* A, int8_t* qA, void* sA, void* fpA, const int32_t* ind, int len,
-                       int zero_outliers, void* stream)
-{
-    if (M < 0 || K <= 0 || len < 0 || (M > 0 && (!A || !qA || !sA))) return MIXQ_E_BADARG;
-    if (len > 0 && (!fpA || !ind)) return MIXQ_E_BADARG;
-    if (K % 8) return MIXQ_E_SHAPE;
-    if (!aligned16(A) || (reinterpret_cast<uintptr_t>(qA) & 7u)) return MIXQ_E_ALIGN;
-    return hip_rc(mixq::launch_quant_extract(A, qA, sA, len > 0 ? fpA : nullptr, ind, M, K, len, zero_outliers != 0,
-                                             static_cast<hipStream_t>(stream)));
+    return mixq_dequant_weight_columns_typed(q_weight, scale_col, ind, len, out, N, K, MIXQ_TYPE_HALF, stream);
 }
 
 int mixq_int8_quantize_with_scale(int rows, int cols, const void* src, const void* scale, int8_t* output, void* stream)
@@ -481,121 +528,116 @@ int mixq_int8_quantize_with_scale(int rows, int cols, const void* src, const voi
     return hip_rc(mixq::launch_quant_with_scale(src, scale, output, rows, cols, static_cast<hipStream_t>(stream)));
 }
 
+// ---- norm producer: RMSNorm of x (of h = x + residual, written to h, when the two are given), optionally with the outlier columns
+// gathered and the row quantised in the same pass ----
+struct NormCall {
+    int M, K, len, quant, q_layout;        // quant: 0 | 8 | 4 (packed pairs); q_layout: MIXQ_QA_* (fragment-major: quant == 8)
+    const void *x, *residual, *gamma;      // residual with h: both or neither
+    void *h, *out, *outliers, *scale, *stream; // outliers [M, len] with ind: both unused when len == 0; scale with q: quant != 0
+    const int32_t* ind;
+    int8_t* q;
+    float eps;
+    bool bf16;                             // every 16-bit operand is bf16 (quant 0 | 8)
+    bool add_required;                     // a named add form: residual and h are operands, not options
+    // legacy: the non-add fp16 layout entry refuses an EMPTY fragment-major call (MIXQ_E_SHAPE) where every sibling answers MIXQ_OK.
+    // Nobody decided that -- it is the code the entry shipped with -- and a caller may depend on either: kept, set by that entry alone
+    bool empty_frag_is_shape;
+};
+
+static int norm_entry(const NormCall& c)
+{
+    const int M = c.M, K = c.K;
+    const bool frag = c.q_layout == MIXQ_QA_FRAGMENT_MAJOR;
+    if (!layout_ok(c.q_layout)) return MIXQ_E_BADARG;
+    if (M < 0 || K <= 0 || c.len < 0 || (c.h && c.h == c.out)) return MIXQ_E_BADARG;
+    if (M > 0 && (!c.x || !c.gamma || !c.out || (c.quant && (!c.q || !c.scale)) || (c.add_required && (!c.residual || !c.h)))) return MIXQ_E_BADARG;
+    if (c.len > 0 && (!c.ind || !c.outliers)) return MIXQ_E_BADARG;
+    if (K % 8 || K > 32768 || (frag && (M > 0 || c.empty_frag_is_shape) && !mixq::quant_frag_layout_supported(M, K))) return MIXQ_E_SHAPE;
+    if (!aligned16(c.x) || !aligned16(c.residual) || !aligned16(c.h) || !aligned16(c.gamma) || !aligned16(c.out) ||
+        misaligned(c.q, c.quant == 4 ? 4 : frag ? 16 : 8))
+        return MIXQ_E_ALIGN;
+    if (M == 0) return MIXQ_OK;
+    return hip_rc(mixq::launch_rmsnorm_quant(c.x, c.gamma, c.out, c.outliers, c.ind, c.q, c.scale, c.eps, M, K, c.len, c.quant,
+                                             static_cast<hipStream_t>(c.stream), frag ? 1 : 0, c.residual, c.h, c.bf16));
+}
+
+// The wrappers build their call from these three: the plain norm, + the gather and the quantised row (quant 8 | 4), + the add
+static NormCall norm_call(int M, int K, const void* x, const void* gamma, void* out, float eps, void* stream)
+{
+    NormCall c{};
+    c.M = M, c.K = K, c.x = x, c.gamma = gamma, c.out = out, c.eps = eps, c.stream = stream;
+    return c;
+}
+static NormCall quantising(NormCall c, const int32_t* ind, int len, void* outliers, void* q, void* scale, int quant, int q_layout)
+{
+    c.ind = ind, c.len = len, c.outliers = outliers, c.q = static_cast<int8_t*>(q), c.scale = scale, c.quant = quant, c.q_layout = q_layout;
+    return c;
+}
+static NormCall adding(NormCall c, const void* residual, void* h, bool required)
+{
+    c.residual = residual, c.h = h, c.add_required = required;
+    return c;
+}
+
 int mixq_rmsnorm(int M, int K, const void* x, const void* gamma, void* out, float eps, void* stream)
 {
-    if (M < 0 || K <= 0 || (M > 0 && (!x || !gamma || !out))) return MIXQ_E_BADARG;
-    if (K % 8 || K > 32768) return MIXQ_E_SHAPE;
-    if (!aligned16(x) || !aligned16(gamma) || !aligned16(out)) return MIXQ_E_ALIGN;
-    return hip_rc(mixq::launch_rmsnorm_quant(x, gamma, out, nullptr, nullptr, nullptr, nullptr, eps, M, K, 0, false,
-                                             static_cast<hipStream_t>(stream)));
+    return norm_entry(norm_call(M, K, x, gamma, out, eps, stream));
 }
-
-int mixq_rmsnorm_extract_quant(int M, int K, const void* x, const void* gamma, void* out, float eps, const int32_t* ind,
-                               int len, void* outliers, int8_t* q, void* scale, void* stream)
+int mixq_rmsnorm_extract_quant(int M, int K, const void* x, const void* gamma, void* out, float eps, const int32_t* ind, int len,
+                               void* outliers, int8_t* q, void* scale, void* stream)
 {
-    if (M < 0 || K <= 0 || len < 0 || (M > 0 && (!x || !gamma || !out || !q || !scale))) return MIXQ_E_BADARG;
-    if (len > 0 && (!ind || !outliers)) return MIXQ_E_BADARG;
-    if (K % 8 || K > 32768) return MIXQ_E_SHAPE;
-    if (!aligned16(x) || !aligned16(gamma) || !aligned16(out) || (reinterpret_cast<uintptr_t>(q) & 7u)) return MIXQ_E_ALIGN;
-    return hip_rc(mixq::launch_rmsnorm_quant(x, gamma, out, outliers, ind, q, scale, eps, M, K, len, 8,
-                                             static_cast<hipStream_t>(stream)));
+    return norm_entry(quantising(norm_call(M, K, x, gamma, out, eps, stream), ind, len, outliers, q, scale, 8, MIXQ_QA_ROW_MAJOR));
 }
-
-int mixq_rmsnorm_extract_quant4(int M, int K, const void* x, const void* gamma, void* out, float eps, const int32_t* ind,
-                                int len, void* outliers, uint8_t* q_packed, void* scale, void* stream)
+int mixq_rmsnorm_extract_quant4(int M, int K, const void* x, const void* gamma, void* out, float eps, const int32_t* ind, int len,
+                                void* outliers, uint8_t* q_packed, void* scale, void* stream)
 {
-    if (M < 0 || K <= 0 || len < 0 || (M > 0 && (!x || !gamma || !out || !q_packed || !scale))) return MIXQ_E_BADARG;
-    if (len > 0 && (!ind || !outliers)) return MIXQ_E_BADARG;
-    if (K % 8 || K > 32768) return MIXQ_E_SHAPE;
-    if (!aligned16(x) || !aligned16(gamma) || !aligned16(out) || (reinterpret_cast<uintptr_t>(q_packed) & 3u))
-        return MIXQ_E_ALIGN;
-    return hip_rc(mixq::launch_rmsnorm_quant(x, gamma, out, outliers, ind, reinterpret_cast<int8_t*>(q_packed), scale, eps,
-                                             M, K, len, 4, static_cast<hipStream_t>(stream)));
+    return norm_entry(quantising(norm_call(M, K, x, gamma, out, eps, stream), ind, len, outliers, q_packed, scale, 4, MIXQ_QA_ROW_MAJOR));
 }
-
-// ---- the residual add in front of the norm, in the norm's pass (MI355X extension): checks as the entries above, in their order ----
+int mixq_rmsnorm_extract_quant_layout(int M, int K, const void* x, const void* gamma, void* out, float eps, const int32_t* ind, int len,
+                                      void* outliers, int8_t* q, void* scale, int q_layout, void* stream)
+{
+    NormCall c = quantising(norm_call(M, K, x, gamma, out, eps, stream), ind, len, outliers, q, scale, 8, q_layout);
+    c.empty_frag_is_shape = true;
+    return norm_entry(c);
+}
+// the residual add in front of the norm, in the norm's pass (MI355X extension)
 int mixq_add_rmsnorm(int M, int K, const void* x, const void* residual, void* h, const void* gamma, void* out, float eps, void* stream)
 {
-    if (M < 0 || K <= 0 || (M > 0 && (!x || !residual || !h || !gamma || !out)) || (h && h == out)) return MIXQ_E_BADARG;
-    if (K % 8 || K > 32768) return MIXQ_E_SHAPE;
-    if (!aligned16(x) || !aligned16(residual) || !aligned16(h) || !aligned16(gamma) || !aligned16(out)) return MIXQ_E_ALIGN;
-    if (M == 0) return MIXQ_OK;
-    return hip_rc(mixq::launch_rmsnorm_quant(x, gamma, out, nullptr, nullptr, nullptr, nullptr, eps, M, K, 0, 0,
-                                             static_cast<hipStream_t>(stream), 0, residual, h));
+    return norm_entry(adding(norm_call(M, K, x, gamma, out, eps, stream), residual, h, true));
 }
-
 int mixq_add_rmsnorm_extract_quant_layout(int M, int K, const void* x, const void* residual, void* h, const void* gamma, void* out,
                                           float eps, const int32_t* ind, int len, void* outliers, int8_t* q, void* scale, int q_layout,
                                           void* stream)
 {
-    const bool frag = q_layout == MIXQ_QA_FRAGMENT_MAJOR;
-    if (q_layout != MIXQ_QA_ROW_MAJOR && !frag) return MIXQ_E_BADARG;
-    if (M < 0 || K <= 0 || len < 0 || (M > 0 && (!x || !residual || !h || !gamma || !out || !q || !scale)) || (h && h == out))
-        return MIXQ_E_BADARG;
-    if (len > 0 && (!ind || !outliers)) return MIXQ_E_BADARG;
-    if (K % 8 || K > 32768 || (frag && M > 0 && !mixq::quant_frag_layout_supported(M, K))) return MIXQ_E_SHAPE;
-    if (!aligned16(x) || !aligned16(residual) || !aligned16(h) || !aligned16(gamma) || !aligned16(out) ||
-        (reinterpret_cast<uintptr_t>(q) & (frag ? 15u : 7u)))
-        return MIXQ_E_ALIGN;
-    if (M == 0) return MIXQ_OK;
-    return hip_rc(mixq::launch_rmsnorm_quant(x, gamma, out, outliers, ind, q, scale, eps, M, K, len, 8,
-                                             static_cast<hipStream_t>(stream), frag ? 1 : 0, residual, h));
+    return norm_entry(adding(quantising(norm_call(M, K, x, gamma, out, eps, stream), ind, len, outliers, q, scale, 8, q_layout), residual, h, true));
 }
-
 int mixq_add_rmsnorm_extract_quant4(int M, int K, const void* x, const void* residual, void* h, const void* gamma, void* out, float eps,
                                     const int32_t* ind, int len, void* outliers, uint8_t* q_packed, void* scale, void* stream)
 {
-    if (M < 0 || K <= 0 || len < 0 || (M > 0 && (!x || !residual || !h || !gamma || !out || !q_packed || !scale)) || (h && h == out))
-        return MIXQ_E_BADARG;
-    if (len > 0 && (!ind || !outliers)) return MIXQ_E_BADARG;
-    if (K % 8 || K > 32768) return MIXQ_E_SHAPE;
-    if (!aligned16(x) || !aligned16(residual) || !aligned16(h) || !aligned16(gamma) || !aligned16(out) ||
-        (reinterpret_cast<uintptr_t>(q_packed) & 3u))
-        return MIXQ_E_ALIGN;
-    if (M == 0) return MIXQ_OK;
-    return hip_rc(mixq::launch_rmsnorm_quant(x, gamma, out, outliers, ind, reinterpret_cast<int8_t*>(q_packed), scale, eps, M, K, len,
-                                             4, static_cast<hipStream_t>(stream), 0, residual, h));
+    return norm_entry(adding(quantising(norm_call(M, K, x, gamma, out, eps, stream), ind, len, outliers, q_packed, scale, 4, MIXQ_QA_ROW_MAJOR),
+                             residual, h, true));
 }
-
-// ---- typed forms of the norm producer (MI355X extension): fp16 = the entries above, bf16 = their checks in their order on bf16 rows ----
-static bool norm_type_ok(int type) { return type == MIXQ_TYPE_HALF || type == MIXQ_TYPE_BF16; }
-
+// typed forms (MI355X extension): the type first, then residual and h together or not at all
 int mixq_rmsnorm_typed(int M, int K, const void* x, const void* residual, void* h, const void* gamma, void* out, float eps, int type,
                        void* stream)
 {
-    if (!norm_type_ok(type)) return MIXQ_E_TYPE;
+    if (!type_ok(type)) return MIXQ_E_TYPE;
     if ((residual == nullptr) != (h == nullptr)) return MIXQ_E_BADARG;
-    if (type == MIXQ_TYPE_HALF)
-        return residual ? mixq_add_rmsnorm(M, K, x, residual, h, gamma, out, eps, stream) : mixq_rmsnorm(M, K, x, gamma, out, eps, stream);
-    if (M < 0 || K <= 0 || (M > 0 && (!x || !gamma || !out)) || (h && h == out)) return MIXQ_E_BADARG;
-    if (K % 8 || K > 32768) return MIXQ_E_SHAPE;
-    if (!aligned16(x) || !aligned16(residual) || !aligned16(h) || !aligned16(gamma) || !aligned16(out)) return MIXQ_E_ALIGN;
-    if (M == 0) return MIXQ_OK;
-    return hip_rc(mixq::launch_rmsnorm_quant(x, gamma, out, nullptr, nullptr, nullptr, nullptr, eps, M, K, 0, 0,
-                                             static_cast<hipStream_t>(stream), 0, residual, h, true));
+    NormCall c = adding(norm_call(M, K, x, gamma, out, eps, stream), residual, h, false);
+    c.bf16 = type == MIXQ_TYPE_BF16;
+    return norm_entry(c);
 }
-
 int mixq_rmsnorm_extract_quant_typed(int M, int K, const void* x, const void* residual, void* h, const void* gamma, void* out, float eps,
                                      const int32_t* ind, int len, void* outliers, int8_t* q, void* scale, int q_layout, int type,
                                      void* stream)
 {
-    if (!norm_type_ok(type)) return MIXQ_E_TYPE;
+    if (!type_ok(type)) return MIXQ_E_TYPE;
     if ((residual == nullptr) != (h == nullptr)) return MIXQ_E_BADARG;
-    if (type == MIXQ_TYPE_HALF)
-        return residual ? mixq_add_rmsnorm_extract_quant_layout(M, K, x, residual, h, gamma, out, eps, ind, len, outliers, q, scale, q_layout,
-                                                                stream)
-                        : mixq_rmsnorm_extract_quant_layout(M, K, x, gamma, out, eps, ind, len, outliers, q, scale, q_layout, stream);
-    const bool frag = q_layout == MIXQ_QA_FRAGMENT_MAJOR;
-    if (q_layout != MIXQ_QA_ROW_MAJOR && !frag) return MIXQ_E_BADARG;
-    if (M < 0 || K <= 0 || len < 0 || (M > 0 && (!x || !gamma || !out || !q || !scale)) || (h && h == out)) return MIXQ_E_BADARG;
-    if (len > 0 && (!ind || !outliers)) return MIXQ_E_BADARG;
-    if (K % 8 || K > 32768 || (frag && M > 0 && !mixq::quant_frag_layout_supported(M, K))) return MIXQ_E_SHAPE;
-    if (!aligned16(x) || !aligned16(residual) || !aligned16(h) || !aligned16(gamma) || !aligned16(out) ||
-        (reinterpret_cast<uintptr_t>(q) & (frag ? 15u : 7u)))
-        return MIXQ_E_ALIGN;
-    if (M == 0) return MIXQ_OK;
-    return hip_rc(mixq::launch_rmsnorm_quant(x, gamma, out, outliers, ind, q, scale, eps, M, K, len, 8, static_cast<hipStream_t>(stream),
-                                             frag ? 1 : 0, residual, h, true));
+    if (type == MIXQ_TYPE_HALF && !residual) // (the named entry, with its kept difference)
+        return mixq_rmsnorm_extract_quant_layout(M, K, x, gamma, out, eps, ind, len, outliers, q, scale, q_layout, stream);
+    NormCall c = adding(quantising(norm_call(M, K, x, gamma, out, eps, stream), ind, len, outliers, q, scale, 8, q_layout), residual, h, false);
+    c.bf16 = type == MIXQ_TYPE_BF16;
+    return norm_entry(c);
 }
 
 // The GemmParams a selection question is asked with: mixq::plan_gemm reads the shape, the qA layout and WHETHER there is scratch and an image
@@ -607,9 +649,22 @@ static mixq::GemmParams plan_probe(int M, int N, int K, int O, int a_frag, const
     return probe;
 }
 
+// The fields every int8 GEMM call fills: operands, scales, addend, output, the zero page and the sizes (O = 0: callers with outlier
+// columns add them).  The zero page may be null here (no device): each entry refuses that where it always did.
+static mixq::GemmParams gemm_params(const void* A, const void* B, const void* sA, const void* sW, const void* Y, void* D, int M, int N, int K)
+{
+    mixq::GemmParams p{};
+    p.A = static_cast<const int8_t*>(A), p.B = static_cast<const int8_t*>(B);
+    p.sA = static_cast<const uint16_t*>(sA), p.sW = static_cast<const uint16_t*>(sW);
+    p.Y = static_cast<const uint16_t*>(Y), p.D = D;
+    p.zeros = mixq::zero_page();
+    p.M = M, p.N = N, p.K = K, p.O = 0;
+    return p;
+}
+
 static int fused_dequant_impl(const int8_t* A, const int8_t* B, const void* scale_row, const void* scale_col,
-                              const void* y, void* D, int M, int N, int K, int epi, void* stream,
-                              const void* mul = nullptr, void* scratch = nullptr, int a_frag = 0)
+                              const void* y, void* D, int M, int N, int K, int epi, void* stream, const void* mul, void* scratch,
+                              int a_frag)
 {
     if (M < 0 || N < 0 || K <= 0) return MIXQ_E_BADARG;
     if (M == 0 || N == 0) return MIXQ_OK;
@@ -617,16 +672,11 @@ static int fused_dequant_impl(const int8_t* A, const int8_t* B, const void* scal
     if (K % 16 || N % 16) return MIXQ_E_SHAPE; // CUTLASS 16-B alignment of the reference
     if (!aligned16(A) || !aligned16(B) || !aligned16(D) || !aligned16(scale_col) || (y && !aligned16(y)))
         return MIXQ_E_ALIGN;
-    mixq::GemmParams p{};
-    p.A = A, p.B = B;
-    p.sA = static_cast<const uint16_t*>(scale_row), p.sW = static_cast<const uint16_t*>(scale_col);
-    p.Y = static_cast<const uint16_t*>(y), p.D = D;
-    p.Mul = static_cast<const uint16_t*>(mul);
     if (epi == mixq::EPI_DEQUANT_SILU_MUL && !mul) return MIXQ_E_BADARG;
     if (epi == mixq::EPI_DEQUANT_SILU_MUL && !aligned16(mul)) return MIXQ_E_ALIGN; // (the ping-pong kernels fetch it 16 bytes at a time)
-    p.zeros = mixq::zero_page();
-    p.M = M, p.N = N, p.K = K, p.O = 0;
+    mixq::GemmParams p = gemm_params(A, B, scale_row, scale_col, y, D, M, N, K);
     if (!p.zeros) return MIXQ_E_HIP;
+    p.Mul = static_cast<const uint16_t*>(mul);
     if (scratch && aligned16(scratch)) p.splitk_ws = scratch; // K split over workgroups where the shape calls for it
     p.a_frag = a_frag;
     if (M <= 64) p.b_image = mixq::resolve_weight_image(B, N, K, static_cast<hipStream_t>(stream)); // (ONE lookup per call)
@@ -638,14 +688,13 @@ static int fused_dequant_impl(const int8_t* A, const int8_t* B, const void* scal
 int mixq_int8_fused_dequantize(const int8_t* A, const int8_t* B, const void* scale_row, const void* scale_col,
                                const void* y, void* D, int M, int N, int K, char* workspace, void* stream)
 {
-    return fused_dequant_impl(A, B, scale_row, scale_col, y, D, M, N, K, mixq::EPI_DEQUANT, stream, nullptr, workspace);
+    return fused_dequant_impl(A, B, scale_row, scale_col, y, D, M, N, K, mixq::EPI_DEQUANT, stream, nullptr, workspace, 0);
 }
 
 int mixq_int8_fused_dequantize_silu(const int8_t* A, const int8_t* B, const void* scale_row, const void* scale_col,
                                     const void* y, void* D, int M, int N, int K, char* workspace, void* stream)
 {
-    return fused_dequant_impl(A, B, scale_row, scale_col, y, D, M, N, K, mixq::EPI_DEQUANT_SILU, stream, nullptr,
-                              workspace);
+    return fused_dequant_impl(A, B, scale_row, scale_col, y, D, M, N, K, mixq::EPI_DEQUANT_SILU, stream, nullptr, workspace, 0);
 }
 
 int mixq_int4quant(int rows, int cols, const void* src, uint8_t* dst, void* scale, void* stream)
@@ -675,7 +724,7 @@ size_t mixq_int4_fused_workspace_size(int M, int N, int k_packed)
 // b8 != nullptr: the weight already widened to int8 [N, 2 k_packed] (once, at load time); only A is unpacked per call
 static int int4_fused_impl(const uint8_t* A, const uint8_t* B, const void* scale_row, const void* scale_col,
                            const void* y, void* D, int M, int N, int k_packed, char* workspace, int epi, void* stream,
-                           const int8_t* b8 = nullptr)
+                           const int8_t* b8)
 {
     if (M < 0 || N < 0 || k_packed <= 0) return MIXQ_E_BADARG;
     if (M == 0 || N == 0) return MIXQ_OK;
@@ -687,12 +736,7 @@ static int int4_fused_impl(const uint8_t* A, const uint8_t* B, const void* scale
     if (B && g_int4_stream.load(std::memory_order_relaxed) && mixq::gemm_skinny_s4_supported(M, N, k_packed)) {
         if (!scale_row || !scale_col || !D) return MIXQ_E_BADARG;
         if (!aligned16(D) || !aligned16(scale_col) || (y && !aligned16(y))) return MIXQ_E_ALIGN;
-        mixq::GemmParams p{};
-        p.A = reinterpret_cast<const int8_t*>(A), p.B = reinterpret_cast<const int8_t*>(B);
-        p.sA = static_cast<const uint16_t*>(scale_row), p.sW = static_cast<const uint16_t*>(scale_col);
-        p.Y = static_cast<const uint16_t*>(y), p.D = D;
-        p.M = M, p.N = N, p.K = k_packed, p.O = 0;
-        return hip_rc(mixq::launch_gemm_skinny_s4(p, epi, st));
+        return hip_rc(mixq::launch_gemm_skinny_s4(gemm_params(A, B, scale_row, scale_col, y, D, M, N, k_packed), epi, st)); // (reads no zero page)
     }
     if (!workspace) return MIXQ_E_WORKSPACE;
     if (!aligned16(workspace)) return MIXQ_E_ALIGN;
@@ -704,7 +748,7 @@ static int int4_fused_impl(const uint8_t* A, const uint8_t* B, const void* scale
         b8 = w8;
     }
     if (e != hipSuccess) return hip_rc(e);
-    return fused_dequant_impl(a8, b8, scale_row, scale_col, y, D, M, N, 2 * k_packed, epi, stream);
+    return fused_dequant_impl(a8, b8, scale_row, scale_col, y, D, M, N, 2 * k_packed, epi, stream, nullptr, nullptr, 0);
 }
 
 // One call for the 4-bit flavour's linear on an fp16 activation (round 6): FindRowScale(bit = 4) + int4FusedDequantize[Silu]
@@ -722,17 +766,13 @@ int mixq_int4_linear_forward(const void* x, const uint8_t* B, void* x_scale, uin
     if (!aligned16(x) || !aligned16(B) || !aligned16(D) || !aligned16(scale_col) || (y && !aligned16(y))) return MIXQ_E_ALIGN;
     const int fq = g_int4_fuse_quant.load(std::memory_order_relaxed);
     if (g_int4_stream.load(std::memory_order_relaxed) && (fq == 2 || (fq == 1 && M == 1)) && mixq::gemm_skinny_s4q_supported(M, N, k_packed)) {
-        mixq::GemmParams p{};
-        p.A = static_cast<const int8_t*>(x), p.B = reinterpret_cast<const int8_t*>(B);
-        p.sA = static_cast<const uint16_t*>(x_scale), p.sW = static_cast<const uint16_t*>(scale_col);
-        p.Y = static_cast<const uint16_t*>(y), p.D = D;
-        p.M = M, p.N = N, p.K = k_packed, p.O = 0;
-        return hip_rc(mixq::launch_gemm_skinny_s4q(p, epilogue, static_cast<hipStream_t>(stream)));
+        return hip_rc(mixq::launch_gemm_skinny_s4q(gemm_params(x, B, x_scale, scale_col, y, D, M, N, k_packed), epilogue,
+                                                   static_cast<hipStream_t>(stream))); // (reads no zero page)
     }
     if (!q_packed) return MIXQ_E_WORKSPACE;
     const int rc = mixq_int4quant(M, 2 * k_packed, x, q_packed, x_scale, stream);
     if (rc != MIXQ_OK) return rc;
-    return int4_fused_impl(q_packed, B, x_scale, scale_col, y, D, M, N, k_packed, workspace, epilogue, stream);
+    return int4_fused_impl(q_packed, B, x_scale, scale_col, y, D, M, N, k_packed, workspace, epilogue, stream, nullptr);
 }
 
 int mixq_int4_fused_dequantize_w8(const uint8_t* A, const int8_t* B_int8, const void* scale_row, const void* scale_col,
@@ -746,13 +786,13 @@ int mixq_int4_fused_dequantize_w8(const uint8_t* A, const int8_t* B_int8, const 
 int mixq_int4_fused_dequantize(const uint8_t* A, const uint8_t* B, const void* scale_row, const void* scale_col,
                                const void* y, void* D, int M, int N, int k_packed, char* workspace, void* stream)
 {
-    return int4_fused_impl(A, B, scale_row, scale_col, y, D, M, N, k_packed, workspace, mixq::EPI_DEQUANT, stream);
+    return int4_fused_impl(A, B, scale_row, scale_col, y, D, M, N, k_packed, workspace, mixq::EPI_DEQUANT, stream, nullptr);
 }
 
 int mixq_int4_fused_dequantize_silu(const uint8_t* A, const uint8_t* B, const void* scale_row, const void* scale_col,
                                     const void* y, void* D, int M, int N, int k_packed, char* workspace, void* stream)
 {
-    return int4_fused_impl(A, B, scale_row, scale_col, y, D, M, N, k_packed, workspace, mixq::EPI_DEQUANT_SILU, stream);
+    return int4_fused_impl(A, B, scale_row, scale_col, y, D, M, N, k_packed, workspace, mixq::EPI_DEQUANT_SILU, stream, nullptr);
 }
 
 int mixq_unpack_int4_to_fp16(const uint8_t* weight, const int32_t* ind, int rows, int cols_packed, int n, void* out,
@@ -776,8 +816,7 @@ int mixq_int8_fused_dequantize_silu_mul(const int8_t* A, const int8_t* B, const 
                                         const void* y, const void* mul, void* D, int M, int N, int K,
                                         char* workspace, void* stream)
 {
-    return fused_dequant_impl(A, B, scale_row, scale_col, y, D, M, N, K, mixq::EPI_DEQUANT_SILU_MUL, stream, mul,
-                              workspace);
+    return fused_dequant_impl(A, B, scale_row, scale_col, y, D, M, N, K, mixq::EPI_DEQUANT_SILU_MUL, stream, mul, workspace, 0);
 }
 
 size_t mixq_gemm_scratch_size(int M, int N, int K) { return gemm_scratch_bytes(M, N, K); }
@@ -788,83 +827,148 @@ size_t mixq_gemm_scratch_bound(void)
     return a > b ? a : b;
 }
 
-int mixq_gemm_mixed(const int8_t* qA, const int8_t* W, const void* sA, const void* sW, const void* fpA,
-                    const void* fpW, void* Out, int M, int N, int K, int O, void* stream)
+// ---- mixed GEMM: Out = dequant(qA W^T) + fpA fpW^T, the outlier product inside the same kernel for up to 128 outlier columns ----
+struct MixedCall {
+    const int8_t *qA, *W;
+    const void *sA, *sW, *fpA, *fpW; // fpA [M, O] / fpW [N, O]: unused when O == 0
+    void *Out, *stream;
+    int M, N, K, O;
+    void* scratch;                   // scratch_bytes of exchange scratch for the K splits over workgroups, or null
+    size_t scratch_bytes;
+    int a_frag;                      // layout of qA (GemmParams::a_frag): the entries' qa_layout; mixq_enqueue: what its quantiser wrote
+    const void* b_image;             // image_resolved: the weight's image has been looked up for this call already (ONE lookup per call)
+    bool image_resolved, bf16;       // bf16: sA, fpA, fpW, bias, mul and Out are bf16 (sW stays fp16)
+    const void* bias;                // the layer's [N] bias of the call's type (the same kernel, one add in its epilogue), or null
+    int act;                         // 0 | EPI_DEQUANT_SILU | EPI_DEQUANT_SILU_MUL with mul, its [M, N] multiplicand of the call's type; never with a bias
+    const void* mul;
+    const mixq::GemmPlan* plan;      // mixq_enqueue has planned this call already (O == kNumOutliers, scratch sized by gemm_scratch_bytes), or null
+};
+
+static MixedCall mixed_call(const int8_t* qA, const int8_t* W, const void* sA, const void* sW, const void* fpA, const void* fpW, void* Out,
+                            int M, int N, int K, int O, void* scratch, size_t scratch_bytes, void* stream)
 {
-    return mixq_gemm_mixed_scratch(qA, W, sA, sW, fpA, fpW, Out, M, N, K, O, nullptr, 0, stream);
+    MixedCall c{}; // (row-major qA, image not looked up, no bias, fp16, not planned, no activation)
+    c.qA = qA, c.W = W, c.sA = sA, c.sW = sW, c.fpA = fpA, c.fpW = fpW, c.Out = Out;
+    c.M = M, c.N = N, c.K = K, c.O = O, c.scratch = scratch, c.scratch_bytes = scratch_bytes, c.stream = stream;
+    return c;
 }
 
-static int gemm_mixed_impl(const int8_t* qA, const int8_t* W, const void* sA, const void* sW, const void* fpA, const void* fpW,
-                           void* Out, int M, int N, int K, int O, void* scratch, size_t scratch_bytes, void* stream,
-                           int a_frag, const void* b_image = nullptr, bool image_resolved = false, const void* bias = nullptr,
-                           bool bf16 = false, const mixq::GemmPlan* plan = nullptr, int act = 0, const void* mul = nullptr);
-
-int mixq_gemm_mixed_scratch(const int8_t* qA, const int8_t* W, const void* sA, const void* sW, const void* fpA,
-                            const void* fpW, void* Out, int M, int N, int K, int O, void* scratch, size_t scratch_bytes,
-                            void* stream)
-{
-    return gemm_mixed_impl(qA, W, sA, sW, fpA, fpW, Out, M, N, K, O, scratch, scratch_bytes, stream, 0);
-}
-
-int mixq_gemm_mixed_bias(const int8_t* qA, const int8_t* W, const void* sA, const void* sW, const void* fpA, const void* fpW,
-                         const void* bias, void* Out, int M, int N, int K, int O, void* scratch, size_t scratch_bytes, void* stream)
-{
-    if (!bias) return MIXQ_E_BADARG;
-    if (!aligned16(bias)) return MIXQ_E_ALIGN;
-    if (O > kNumOutliers) return MIXQ_E_SHAPE; // (the two-step order of more outlier columns feeds an addend; the bias form takes none)
-    return gemm_mixed_impl(qA, W, sA, sW, fpA, fpW, Out, M, N, K, O, scratch, scratch_bytes, stream, 0, nullptr, false, bias);
-}
-
-// the epilogue of a mixed GEMM with 128 outlier columns at most (act: 0 | EPI_DEQUANT_SILU | EPI_DEQUANT_SILU_MUL, never with a bias)
-static int mixed_epi(bool bias, bool bf16, int act = 0)
+// the epilogue of a mixed GEMM with 128 outlier columns at most
+static int mixed_epi(bool bias, bool bf16, int act)
 {
     if (act == mixq::EPI_DEQUANT_SILU) return bf16 ? mixq::EPI_DEQUANT_SILU_BF16 : mixq::EPI_DEQUANT_SILU;
     if (act == mixq::EPI_DEQUANT_SILU_MUL) return bf16 ? mixq::EPI_DEQUANT_SILU_MUL_BF16 : mixq::EPI_DEQUANT_SILU_MUL;
     return bf16 ? (bias ? mixq::EPI_DEQUANT_BIAS_BF16 : mixq::EPI_DEQUANT_BF16) : (bias ? mixq::EPI_DEQUANT_BIAS : mixq::EPI_DEQUANT);
 }
 
-// a_frag: layout of qA (GemmParams::a_frag): enqueue's own quantiser may write the consuming kernel's preferred image; the
-// public entries take row-major qA
-// b_image / image_resolved: the caller has already looked the weight's image up for this call (one lookup per call)
-// bias: the layer's fp16 [N] bias (EPI_DEQUANT_BIAS: the same kernel as EPI_DEQUANT, one fp16 add in its epilogue), or null
-// plan: mixq_enqueue has planned this call already (O == kNumOutliers, scratch sized by gemm_scratch_bytes), or null
-// act / mul: mixq_gemm_mixed_act_typed's activation (0 | EPI_DEQUANT_SILU | EPI_DEQUANT_SILU_MUL with its [M, N] multiplicand of the call's type)
-static int gemm_mixed_impl(const int8_t* qA, const int8_t* W, const void* sA, const void* sW, const void* fpA, const void* fpW,
-                           void* Out, int M, int N, int K, int O, void* scratch, size_t scratch_bytes, void* stream,
-                           int a_frag, const void* b_image, bool image_resolved, const void* bias, bool bf16, const mixq::GemmPlan* plan,
-                           int act, const void* mul)
+// Argument values and shapes of a mixed call; MIXQ_OK for an empty one as well (the caller returns on M == 0 || N == 0)
+static int mixed_args_rc(const MixedCall& c)
 {
-    if (M < 0 || N < 0 || K <= 0 || O < 0) return MIXQ_E_BADARG;
-    if (M == 0 || N == 0) return MIXQ_OK;
-    if (!qA || !W || !sA || !sW || !Out || (O > 0 && (!fpA || !fpW))) return MIXQ_E_BADARG;
-    if (K % 16 || N % 16 || O % 8) return MIXQ_E_SHAPE;
-    if (!aligned16(qA) || !aligned16(W) || !aligned16(Out) || !aligned16(sW) || (O > 0 && (!aligned16(fpA) || !aligned16(fpW))))
+    if (c.M < 0 || c.N < 0 || c.K <= 0 || c.O < 0) return MIXQ_E_BADARG;
+    if (c.M == 0 || c.N == 0) return MIXQ_OK;
+    if (!c.qA || !c.W || !c.sA || !c.sW || !c.Out || (c.O > 0 && (!c.fpA || !c.fpW))) return MIXQ_E_BADARG;
+    if (c.K % 16 || c.N % 16 || c.O % 8) return MIXQ_E_SHAPE;
+    return MIXQ_OK;
+}
+
+static int gemm_mixed_impl(const MixedCall& c)
+{
+    const int rc = mixed_args_rc(c);
+    if (rc != MIXQ_OK || c.M == 0 || c.N == 0) return rc;
+    if (!aligned16(c.qA) || !aligned16(c.W) || !aligned16(c.Out) || !aligned16(c.sW) || (c.O > 0 && (!aligned16(c.fpA) || !aligned16(c.fpW))))
         return MIXQ_E_ALIGN;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    mixq::GemmParams p{};
-    p.A = qA, p.B = W;
-    p.sA = static_cast<const uint16_t*>(sA), p.sW = static_cast<const uint16_t*>(sW);
-    p.D = Out;
-    p.zeros = mixq::zero_page();
+    hipStream_t st = static_cast<hipStream_t>(c.stream);
+    mixq::GemmParams p = gemm_params(c.qA, c.W, c.sA, c.sW, nullptr, c.Out, c.M, c.N, c.K);
     if (!p.zeros) return MIXQ_E_HIP;
-    p.M = M, p.N = N, p.K = K;
     p.dbg = g_dbg_stamps.load(std::memory_order_relaxed);
-    p.a_frag = a_frag;
-    p.b_image = image_resolved ? b_image : (M <= 64 ? mixq::resolve_weight_image(W, N, K, st) : nullptr);
-    if (scratch && aligned16(scratch) && (plan || scratch_bytes >= gemm_scratch_bytes(M, N, K))) p.splitk_ws = scratch;
-    if (O <= kNumOutliers) {
-        p.fpA = static_cast<const uint16_t*>(fpA), p.fpW = static_cast<const uint16_t*>(fpW), p.O = O;
-        p.bias = static_cast<const uint16_t*>(bias);
-        p.Mul = static_cast<const uint16_t*>(mul);
-        g_last_gemm_bf16.store(bf16, std::memory_order_relaxed);
-        return hip_rc(mixq::launch_gemm(p, mixed_epi(bias != nullptr, bf16, act), st, plan));
+    p.a_frag = c.a_frag;
+    p.b_image = c.image_resolved ? c.b_image : (c.M <= 64 ? mixq::resolve_weight_image(c.W, c.N, c.K, st) : nullptr);
+    if (c.scratch && aligned16(c.scratch) && (c.plan || c.scratch_bytes >= gemm_scratch_bytes(c.M, c.N, c.K))) p.splitk_ws = c.scratch;
+    if (c.O <= kNumOutliers) {
+        p.fpA = static_cast<const uint16_t*>(c.fpA), p.fpW = static_cast<const uint16_t*>(c.fpW), p.O = c.O;
+        p.bias = static_cast<const uint16_t*>(c.bias);
+        p.Mul = static_cast<const uint16_t*>(c.mul);
+        g_last_gemm_bf16.store(c.bf16, std::memory_order_relaxed);
+        return hip_rc(mixq::launch_gemm(p, mixed_epi(c.bias != nullptr, c.bf16, c.act), st, c.plan));
     }
-    if (bias || bf16 || act) return MIXQ_E_SHAPE;
+    if (c.bias || c.bf16 || c.act) return MIXQ_E_SHAPE;
     // more outlier columns than one LDS pass holds: the reference's own two-step order (side GEMM into Out, then C = D = Out)
-    hipError_t e = mixq::launch_gemm_fp16(fpA, fpW, Out, M, N, O, st);
+    hipError_t e = mixq::launch_gemm_fp16(c.fpA, c.fpW, c.Out, c.M, c.N, c.O, st);
     if (e != hipSuccess) return MIXQ_E_HIP;
-    p.Y = static_cast<const uint16_t*>(Out), p.O = 0;
+    p.Y = static_cast<const uint16_t*>(c.Out);
     return hip_rc(mixq::launch_gemm(p, mixq::EPI_DEQUANT, st));
+}
+
+// A fragment-major qA has ONE reader, the skinny kernel: looks the weight's image up (for the launch as well) and refuses the call
+// (MIXQ_E_SHAPE) unless its plan, with the scratch it really has, is that kernel
+static int mixed_frag_gate(MixedCall& c)
+{
+    if (c.O > kNumOutliers || c.M <= 0 || c.N <= 0 || c.K <= 0 || !c.W) return MIXQ_E_SHAPE;
+    c.b_image = mixq::resolve_weight_image(c.W, c.N, c.K, static_cast<hipStream_t>(c.stream));
+    c.image_resolved = true;
+    const size_t need = gemm_scratch_bytes(c.M, c.N, c.K);
+    const mixq::GemmParams probe =
+        plan_probe(c.M, c.N, c.K, c.O, 1, c.scratch && need && c.scratch_bytes >= need ? c.scratch : nullptr, c.b_image);
+    return mixq::gemm_takes_skinny(probe, mixq::EPI_DEQUANT) ? MIXQ_OK : MIXQ_E_SHAPE;
+}
+
+// The launcher-level fused GEMM by type and layout; the bias form's checks in front when a bias is given.  The forms below are this call
+// with fewer operands: bf16 = the same checks and the same kernel choice with the bf16 epilogues
+int mixq_gemm_mixed_typed(const int8_t* qA, const int8_t* W, const void* sA, const void* sW, const void* fpA, const void* fpW,
+                          const void* bias, void* Out, int M, int N, int K, int O, int qa_layout, int type, void* scratch,
+                          size_t scratch_bytes, void* stream)
+{
+    if (!type_ok(type)) return MIXQ_E_TYPE;
+    if (!layout_ok(qa_layout)) return MIXQ_E_BADARG;
+    MixedCall c = mixed_call(qA, W, sA, sW, fpA, fpW, Out, M, N, K, O, scratch, scratch_bytes, stream);
+    c.a_frag = qa_layout, c.bias = bias, c.bf16 = type == MIXQ_TYPE_BF16;
+    if (bias && !aligned16(bias)) return MIXQ_E_ALIGN;
+    if ((bias || c.bf16) && O > kNumOutliers) return MIXQ_E_SHAPE; // (the two-step order of more outlier columns feeds an addend; these epilogues take none)
+    if (qa_layout == MIXQ_QA_FRAGMENT_MAJOR && mixed_frag_gate(c) != MIXQ_OK) return MIXQ_E_SHAPE;
+    return gemm_mixed_impl(c);
+}
+
+int mixq_gemm_mixed_layout(const int8_t* qA, const int8_t* W, const void* sA, const void* sW, const void* fpA, const void* fpW,
+                           void* Out, int M, int N, int K, int O, int qa_layout, void* scratch, size_t scratch_bytes, void* stream)
+{
+    return mixq_gemm_mixed_typed(qA, W, sA, sW, fpA, fpW, nullptr, Out, M, N, K, O, qa_layout, MIXQ_TYPE_HALF, scratch, scratch_bytes, stream);
+}
+int mixq_gemm_mixed_scratch(const int8_t* qA, const int8_t* W, const void* sA, const void* sW, const void* fpA, const void* fpW, void* Out,
+                            int M, int N, int K, int O, void* scratch, size_t scratch_bytes, void* stream)
+{
+    return mixq_gemm_mixed_layout(qA, W, sA, sW, fpA, fpW, Out, M, N, K, O, MIXQ_QA_ROW_MAJOR, scratch, scratch_bytes, stream);
+}
+int mixq_gemm_mixed(const int8_t* qA, const int8_t* W, const void* sA, const void* sW, const void* fpA, const void* fpW, void* Out, int M,
+                    int N, int K, int O, void* stream)
+{
+    return mixq_gemm_mixed_scratch(qA, W, sA, sW, fpA, fpW, Out, M, N, K, O, nullptr, 0, stream);
+}
+int mixq_gemm_mixed_bias(const int8_t* qA, const int8_t* W, const void* sA, const void* sW, const void* fpA, const void* fpW,
+                         const void* bias, void* Out, int M, int N, int K, int O, void* scratch, size_t scratch_bytes, void* stream)
+{
+    if (!bias) return MIXQ_E_BADARG; // (this form's own: to the typed entry a null bias is no bias)
+    return mixq_gemm_mixed_typed(qA, W, sA, sW, fpA, fpW, bias, Out, M, N, K, O, MIXQ_QA_ROW_MAJOR, MIXQ_TYPE_HALF, scratch, scratch_bytes, stream);
+}
+
+// mixq_gemm_mixed_typed with an activation in the epilogue of the SAME kernel (the plan is EPI_DEQUANT's): SiLU, or SiLU then one multiply
+// of the rounded value by `mul`.  The checks run by class -- type, arguments, shapes, alignment -- as the header states them.
+int mixq_gemm_mixed_act_typed(const int8_t* qA, const int8_t* W, const void* sA, const void* sW, const void* fpA, const void* fpW,
+                              const void* mul, void* Out, int M, int N, int K, int O, int epilogue, int qa_layout, int type,
+                              void* scratch, size_t scratch_bytes, void* stream)
+{
+    if (!type_ok(type)) return MIXQ_E_TYPE;
+    if (epilogue != mixq::EPI_DEQUANT && epilogue != mixq::EPI_DEQUANT_SILU && epilogue != mixq::EPI_DEQUANT_SILU_MUL) return MIXQ_E_BADARG;
+    if ((epilogue == mixq::EPI_DEQUANT_SILU_MUL) != (mul != nullptr)) return MIXQ_E_BADARG;
+    if (mul && Out == mul) return MIXQ_E_BADARG; // (a lane's 16-byte fetch of mul covers elements other lanes store)
+    if (!layout_ok(qa_layout)) return MIXQ_E_BADARG;
+    MixedCall c = mixed_call(qA, W, sA, sW, fpA, fpW, Out, M, N, K, O, scratch, scratch_bytes, stream);
+    c.a_frag = qa_layout, c.bf16 = type == MIXQ_TYPE_BF16, c.act = epilogue, c.mul = mul;
+    const int rc = mixed_args_rc(c);
+    if (rc != MIXQ_OK || M == 0 || N == 0) return rc;
+    if (O > kNumOutliers && (c.act || c.bf16)) return MIXQ_E_SHAPE; // (one LDS pass of outlier columns: no addend form)
+    if (qa_layout == MIXQ_QA_FRAGMENT_MAJOR && mixed_frag_gate(c) != MIXQ_OK) return MIXQ_E_SHAPE;
+    if (mul && !aligned16(mul)) return MIXQ_E_ALIGN; // (the ping-pong kernels fetch it 16 bytes at a time)
+    return gemm_mixed_impl(c);
 }
 
 // ---- weight images (MI355X extension): a fragment-major copy of `weight` for the decode-batch GEMM ------------------------------
@@ -912,114 +1016,14 @@ size_t mixq_qa_bytes(int M, int K, int layout)
     return (size_t)M * (size_t)K;
 }
 
-int mixq_quant_extract_layout(int M, int K, void* A, int8_t* qA, void* sA, void* fpA, const int32_t* ind, int len,
-                              int zero_outliers, int q_layout, void* stream)
-{
-    if (q_layout == MIXQ_QA_ROW_MAJOR) return mixq_quant_extract(M, K, A, qA, sA, fpA, ind, len, zero_outliers, stream);
-    if (q_layout != MIXQ_QA_FRAGMENT_MAJOR) return MIXQ_E_BADARG;
-    if (M < 0 || K <= 0 || len < 0 || (M > 0 && (!A || !qA || !sA))) return MIXQ_E_BADARG;
-    if (len > 0 && (!fpA || !ind)) return MIXQ_E_BADARG;
-    if (K % 8 || !mixq::quant_frag_layout_supported(M, K)) return MIXQ_E_SHAPE;
-    if (!aligned16(A) || !aligned16(qA)) return MIXQ_E_ALIGN;
-    return hip_rc(mixq::launch_quant_extract(A, qA, sA, len > 0 ? fpA : nullptr, ind, M, K, len, zero_outliers != 0,
-                                             static_cast<hipStream_t>(stream), nullptr, 1));
-}
-
-int mixq_rmsnorm_extract_quant_layout(int M, int K, const void* x, const void* gamma, void* out, float eps, const int32_t* ind,
-                                      int len, void* outliers, int8_t* q, void* scale, int q_layout, void* stream)
-{
-    if (q_layout == MIXQ_QA_ROW_MAJOR) return mixq_rmsnorm_extract_quant(M, K, x, gamma, out, eps, ind, len, outliers, q, scale, stream);
-    if (q_layout != MIXQ_QA_FRAGMENT_MAJOR) return MIXQ_E_BADARG;
-    if (M < 0 || K <= 0 || len < 0 || (M > 0 && (!x || !gamma || !out || !q || !scale))) return MIXQ_E_BADARG;
-    if (len > 0 && (!ind || !outliers)) return MIXQ_E_BADARG;
-    if (K % 8 || K > 32768 || !mixq::quant_frag_layout_supported(M, K)) return MIXQ_E_SHAPE;
-    if (!aligned16(x) || !aligned16(gamma) || !aligned16(out) || !aligned16(q)) return MIXQ_E_ALIGN;
-    return hip_rc(mixq::launch_rmsnorm_quant(x, gamma, out, outliers, ind, q, scale, eps, M, K, len, 8,
-                                             static_cast<hipStream_t>(stream), 1));
-}
-
 int mixq_int8_fused_dequantize_layout(const int8_t* A, const int8_t* B, const void* scale_row, const void* scale_col,
                                       const void* y, const void* mul, void* D, int M, int N, int K, int epilogue, int qa_layout,
                                       char* workspace, void* stream)
 {
     if (epilogue != mixq::EPI_DEQUANT && epilogue != mixq::EPI_DEQUANT_SILU && epilogue != mixq::EPI_DEQUANT_SILU_MUL)
         return MIXQ_E_BADARG;
-    if (qa_layout != MIXQ_QA_ROW_MAJOR && qa_layout != MIXQ_QA_FRAGMENT_MAJOR) return MIXQ_E_BADARG;
+    if (!layout_ok(qa_layout)) return MIXQ_E_BADARG;
     return fused_dequant_impl(A, B, scale_row, scale_col, y, D, M, N, K, epilogue, stream, mul, workspace, qa_layout);
-}
-
-int mixq_gemm_mixed_layout(const int8_t* qA, const int8_t* W, const void* sA, const void* sW, const void* fpA, const void* fpW,
-                           void* Out, int M, int N, int K, int O, int qa_layout, void* scratch, size_t scratch_bytes, void* stream)
-{
-    if (qa_layout != MIXQ_QA_ROW_MAJOR && qa_layout != MIXQ_QA_FRAGMENT_MAJOR) return MIXQ_E_BADARG;
-    const void* img = nullptr;
-    bool resolved = false;
-    if (qa_layout == MIXQ_QA_FRAGMENT_MAJOR) {
-        if (O > kNumOutliers || M <= 0 || N <= 0 || K <= 0 || !W) return MIXQ_E_SHAPE;
-        img = mixq::resolve_weight_image(W, N, K, static_cast<hipStream_t>(stream));
-        resolved = true;
-        const size_t need = gemm_scratch_bytes(M, N, K);
-        const mixq::GemmParams probe = plan_probe(M, N, K, O, 1, scratch && need && scratch_bytes >= need ? scratch : nullptr, img);
-        if (!mixq::gemm_takes_skinny(probe, mixq::EPI_DEQUANT)) return MIXQ_E_SHAPE; // (the image has ONE reader)
-    }
-    return gemm_mixed_impl(qA, W, sA, sW, fpA, fpW, Out, M, N, K, O, scratch, scratch_bytes, stream, qa_layout, img, resolved);
-}
-
-// the launcher-level fused GEMM by type: fp16 = mixq_gemm_mixed_layout (mixq_gemm_mixed_bias's checks in front when a bias is given),
-// bf16 = the same checks and the same kernel choice with the bf16 epilogues (sA, fpA, fpW, bias and Out bf16; sW fp16)
-int mixq_gemm_mixed_typed(const int8_t* qA, const int8_t* W, const void* sA, const void* sW, const void* fpA, const void* fpW,
-                          const void* bias, void* Out, int M, int N, int K, int O, int qa_layout, int type, void* scratch,
-                          size_t scratch_bytes, void* stream)
-{
-    if (type != MIXQ_TYPE_HALF && type != MIXQ_TYPE_BF16) return MIXQ_E_TYPE;
-    const bool bf16 = type == MIXQ_TYPE_BF16;
-    if (!bf16 && !bias) return mixq_gemm_mixed_layout(qA, W, sA, sW, fpA, fpW, Out, M, N, K, O, qa_layout, scratch, scratch_bytes, stream);
-    if (qa_layout != MIXQ_QA_ROW_MAJOR && qa_layout != MIXQ_QA_FRAGMENT_MAJOR) return MIXQ_E_BADARG;
-    if (bias && !aligned16(bias)) return MIXQ_E_ALIGN;
-    if (O > kNumOutliers) return MIXQ_E_SHAPE; // (one LDS pass of outlier columns: the bias and the bf16 epilogues take no addend)
-    const void* img = nullptr;
-    bool resolved = false;
-    if (qa_layout == MIXQ_QA_FRAGMENT_MAJOR) {
-        if (M <= 0 || N <= 0 || K <= 0 || !W) return MIXQ_E_SHAPE;
-        img = mixq::resolve_weight_image(W, N, K, static_cast<hipStream_t>(stream));
-        resolved = true;
-        const size_t need = gemm_scratch_bytes(M, N, K);
-        const mixq::GemmParams probe = plan_probe(M, N, K, O, 1, scratch && need && scratch_bytes >= need ? scratch : nullptr, img);
-        if (!mixq::gemm_takes_skinny(probe, mixq::EPI_DEQUANT)) return MIXQ_E_SHAPE; // (the image has ONE reader)
-    }
-    return gemm_mixed_impl(qA, W, sA, sW, fpA, fpW, Out, M, N, K, O, scratch, scratch_bytes, stream, qa_layout, img, resolved, bias, bf16);
-}
-
-// mixq_gemm_mixed_typed with an activation in the epilogue of the SAME kernel (the plan is EPI_DEQUANT's): SiLU, or SiLU then one multiply
-// of the rounded value by `mul`.  The checks run by class -- type, arguments, shapes, alignment -- as the header states them.
-int mixq_gemm_mixed_act_typed(const int8_t* qA, const int8_t* W, const void* sA, const void* sW, const void* fpA, const void* fpW,
-                              const void* mul, void* Out, int M, int N, int K, int O, int epilogue, int qa_layout, int type,
-                              void* scratch, size_t scratch_bytes, void* stream)
-{
-    if (type != MIXQ_TYPE_HALF && type != MIXQ_TYPE_BF16) return MIXQ_E_TYPE;
-    const bool bf16 = type == MIXQ_TYPE_BF16;
-    if (epilogue != mixq::EPI_DEQUANT && epilogue != mixq::EPI_DEQUANT_SILU && epilogue != mixq::EPI_DEQUANT_SILU_MUL) return MIXQ_E_BADARG;
-    if ((epilogue == mixq::EPI_DEQUANT_SILU_MUL) != (mul != nullptr)) return MIXQ_E_BADARG;
-    if (mul && Out == mul) return MIXQ_E_BADARG; // (a lane's 16-byte fetch of mul covers elements other lanes store)
-    if (qa_layout != MIXQ_QA_ROW_MAJOR && qa_layout != MIXQ_QA_FRAGMENT_MAJOR) return MIXQ_E_BADARG;
-    if (M < 0 || N < 0 || K <= 0 || O < 0) return MIXQ_E_BADARG;
-    if (M == 0 || N == 0) return MIXQ_OK;
-    if (!qA || !W || !sA || !sW || !Out || (O > 0 && (!fpA || !fpW))) return MIXQ_E_BADARG;
-    if (K % 16 || N % 16 || O % 8) return MIXQ_E_SHAPE;
-    if (O > kNumOutliers && (epilogue != mixq::EPI_DEQUANT || bf16)) return MIXQ_E_SHAPE; // (one LDS pass of outlier columns: no addend form)
-    const void* img = nullptr;
-    bool resolved = false;
-    if (qa_layout == MIXQ_QA_FRAGMENT_MAJOR) {
-        if (O > kNumOutliers) return MIXQ_E_SHAPE;
-        img = mixq::resolve_weight_image(W, N, K, static_cast<hipStream_t>(stream));
-        resolved = true;
-        const size_t need = gemm_scratch_bytes(M, N, K);
-        const mixq::GemmParams probe = plan_probe(M, N, K, O, 1, scratch && need && scratch_bytes >= need ? scratch : nullptr, img);
-        if (!mixq::gemm_takes_skinny(probe, mixq::EPI_DEQUANT)) return MIXQ_E_SHAPE; // (the image has ONE reader)
-    }
-    if (mul && !aligned16(mul)) return MIXQ_E_ALIGN; // (the ping-pong kernels fetch it 16 bytes at a time)
-    return gemm_mixed_impl(qA, W, sA, sW, fpA, fpW, Out, M, N, K, O, scratch, scratch_bytes, stream, qa_layout, img, resolved, nullptr, bf16,
-                           nullptr, epilogue, mul);
 }
 
 int mixq_mixlinear_forward(int M, int N, int K, int O, void* x, const int32_t* ind, const int8_t* q_weight,
@@ -1050,57 +1054,19 @@ int mixq_mixlinear_forward(int M, int N, int K, int O, void* x, const int32_t* i
                                       stream);
 }
 
-// ---- typed forms of the P-flavour's entries (MI355X extension): fp16 = the named entry, bf16 = its checks in its order on bf16 rows ----
-int mixq_quant_extract_typed(int M, int K, void* A, int8_t* qA, void* sA, void* fpA, const int32_t* ind, int len, int zero_outliers,
-                             int q_layout, int type, void* stream)
-{
-    if (!norm_type_ok(type)) return MIXQ_E_TYPE;
-    if (type == MIXQ_TYPE_HALF) return mixq_quant_extract_layout(M, K, A, qA, sA, fpA, ind, len, zero_outliers, q_layout, stream);
-    const bool frag = q_layout == MIXQ_QA_FRAGMENT_MAJOR;
-    if (q_layout != MIXQ_QA_ROW_MAJOR && !frag) return MIXQ_E_BADARG;
-    if (M < 0 || K <= 0 || len < 0 || (M > 0 && (!A || !qA || !sA))) return MIXQ_E_BADARG;
-    if (len > 0 && (!fpA || !ind)) return MIXQ_E_BADARG;
-    if (K % 8 || (frag && !mixq::quant_frag_layout_supported(M, K))) return MIXQ_E_SHAPE;
-    if (!aligned16(A) || (reinterpret_cast<uintptr_t>(qA) & (frag ? 15u : 7u))) return MIXQ_E_ALIGN;
-    return hip_rc(mixq::launch_quant_extract(A, qA, sA, len > 0 ? fpA : nullptr, ind, M, K, len, zero_outliers != 0,
-                                             static_cast<hipStream_t>(stream), nullptr, frag ? 1 : 0, true));
-}
-
-int mixq_find_outliers_typed(const void* A, int M, int K, float sigma, void* mask_ws, int32_t* ind_out, int32_t* count_out, int capacity,
-                             int type, void* stream)
-{
-    if (!norm_type_ok(type)) return MIXQ_E_TYPE;
-    if (type == MIXQ_TYPE_HALF) return mixq_find_outliers(A, M, K, sigma, mask_ws, ind_out, count_out, capacity, stream);
-    if (M < 0 || K <= 0 || capacity < 0 || !mask_ws || !count_out || (capacity > 0 && !ind_out) || (M > 0 && !A))
-        return MIXQ_E_BADARG;
-    if (K % 8) return MIXQ_E_SHAPE;
-    if (M > 0 && !aligned16(A)) return MIXQ_E_ALIGN;
-    return hip_rc(mixq::launch_find_outliers(A, M, K, sigma, static_cast<unsigned*>(mask_ws), ind_out, count_out, capacity,
-                                             static_cast<hipStream_t>(stream), true));
-}
-
-int mixq_dequant_weight_columns_typed(const int8_t* q_weight, const void* scale_col, const int32_t* ind, int len, void* out, int N, int K,
-                                      int type, void* stream)
-{
-    if (!norm_type_ok(type)) return MIXQ_E_TYPE;
-    if (type == MIXQ_TYPE_HALF) return mixq_dequant_weight_columns(q_weight, scale_col, ind, len, out, N, K, stream);
-    if (N < 0 || K <= 0 || len < 0 || (N > 0 && len > 0 && (!q_weight || !scale_col || !ind || !out)))
-        return MIXQ_E_BADARG;
-    return hip_rc(mixq::launch_dequant_columns(q_weight, scale_col, ind, len, out, N, K, static_cast<hipStream_t>(stream), true));
-}
-
+// ---- the typed form (MI355X extension): fp16 = the entry above ----
 int mixq_mixlinear_forward_typed(int M, int N, int K, int O, void* x, const int32_t* ind, const int8_t* q_weight, const void* scale_col,
                                  const void* weight_cache, void* x_scale, int8_t* q_x, void* outliers, void* out, int q_layout, int type,
                                  void* scratch, size_t scratch_bytes, void* stream)
 {
-    if (!norm_type_ok(type)) return MIXQ_E_TYPE;
+    if (!type_ok(type)) return MIXQ_E_TYPE;
     if (type == MIXQ_TYPE_HALF)
         return mixq_mixlinear_forward(M, N, K, O, x, ind, q_weight, scale_col, weight_cache, x_scale, q_x, outliers, out, q_layout, scratch,
                                       scratch_bytes, stream);
     // bf16: the zeroing quantiser on bf16 rows, then what mixq_gemm_mixed_typed(.., bias = NULL, MIXQ_TYPE_BF16) launches.  The first launch
     // writes x, so EVERY refusal of either step is made here, before it: a refused call leaves x as it was.
     const bool frag = q_layout == MIXQ_QA_FRAGMENT_MAJOR;
-    if (M < 0 || N < 0 || K <= 0 || O < 0 || (q_layout != MIXQ_QA_ROW_MAJOR && !frag)) return MIXQ_E_BADARG;
+    if (M < 0 || N < 0 || K <= 0 || O < 0 || !layout_ok(q_layout)) return MIXQ_E_BADARG;
     if (M == 0 || N == 0) return MIXQ_OK;
     if (!x || !q_weight || !scale_col || !x_scale || !q_x || !out || (O > 0 && (!ind || !weight_cache || !outliers)))
         return MIXQ_E_BADARG;
@@ -1109,8 +1075,7 @@ int mixq_mixlinear_forward_typed(int M, int N, int K, int O, void* x, const int3
     if (frag && mixq_qa_layout(M, N, K) != MIXQ_QA_FRAGMENT_MAJOR) return MIXQ_E_SHAPE;
     if (!aligned16(x) || !aligned16(q_x) || !aligned16(q_weight) || !aligned16(out) || !aligned16(scale_col) || (O > 0 && (!aligned16(outliers) || !aligned16(weight_cache))))
         return MIXQ_E_ALIGN;
-    int rc = hip_rc(mixq::launch_quant_extract(x, q_x, x_scale, O > 0 ? outliers : nullptr, ind, M, K, O, true,
-                                               static_cast<hipStream_t>(stream), nullptr, frag ? 1 : 0, true));
+    const int rc = mixq_quant_extract_typed(M, K, x, q_x, x_scale, outliers, ind, O, 1, q_layout, MIXQ_TYPE_BF16, stream); // (refuses nothing: all of it was checked above)
     if (rc != MIXQ_OK) return rc;
     return mixq_gemm_mixed_typed(q_x, q_weight, x_scale, scale_col, outliers, weight_cache, nullptr, out, M, N, K, O, q_layout,
                                  MIXQ_TYPE_BF16, frag ? nullptr : scratch, frag ? 0 : scratch_bytes, stream);
@@ -1123,11 +1088,8 @@ int mixq_gemm_s8s8s32(const int8_t* A, const int8_t* B, int32_t* C, int M, int N
     if (!A || !B || !C) return MIXQ_E_BADARG;
     if (K % 16 || N % 16) return MIXQ_E_SHAPE;
     if (!aligned16(A) || !aligned16(B) || !aligned16(C)) return MIXQ_E_ALIGN;
-    mixq::GemmParams p{};
-    p.A = A, p.B = B, p.D = C;
-    p.zeros = mixq::zero_page();
+    const mixq::GemmParams p = gemm_params(A, B, nullptr, nullptr, nullptr, C, M, N, K);
     if (!p.zeros) return MIXQ_E_HIP;
-    p.M = M, p.N = N, p.K = K, p.O = 0;
     return hip_rc(mixq::launch_gemm(p, mixq::EPI_INT32, static_cast<hipStream_t>(stream)));
 }
 
@@ -1208,9 +1170,25 @@ static mixq::GemmPlan enqueue_plan(int64_t M, int64_t N, int64_t K, int epi, voi
     return plan;
 }
 
+// M <= 4: one launch on qweight, the GEMV or the fpA_intB skinny form -- the two forms mixq_w8a16_gemm_forward picks from (the plain
+// fp16 call IS that entry), with the bias and for bf16 calls as well
+static int enqueue_small_m(const void* A, const uint8_t* q_weight, const void* scales, void* Out, int M, int N, int K, const void* bias,
+                           bool bf16, void* stream)
+{
+    if (!bf16 && !bias) return mixq_w8a16_gemm_forward(A, q_weight, scales, Out, M, N, K, stream);
+    if (K % 64 || N % 2) return MIXQ_E_SHAPE;
+    if (!aligned16(A) || !aligned16(q_weight)) return MIXQ_E_ALIGN;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (!mixq::w8a16_skinny_takes(M, N, K))
+        return hip_rc(bf16 ? mixq::launch_w8a16_bf16(A, q_weight, scales, Out, M, N, K, st, bias) : mixq::launch_w8a16(A, q_weight, scales, Out, M, N, K, st, bias));
+    if (K % 8 || !w8a16_out_aligned(Out, N)) return MIXQ_E_ALIGN;
+    return hip_rc(bf16 ? mixq::launch_w8a16_skinny_bf16(A, q_weight, scales, Out, M, N, K, bias, st)
+                       : mixq::launch_w8a16_skinny_bias(A, q_weight, scales, Out, M, N, K, bias, st));
+}
+
 static int enqueue_impl(const mixq_handle* h, const mixq_tensor_desc* inputDesc, const void* const* inputs,
                         void* const* outputs, void* workspace, void* stream, void* ev_gemm_start, void* ev_gemm_stop,
-                        const void* bias = nullptr, const mixq_tensor_desc* outputDesc = nullptr)
+                        const void* bias, const mixq_tensor_desc* outputDesc)
 {
     if (!h || !inputDesc || !inputs || !outputs) return MIXQ_E_BADARG;
     // bf16 call: A, fp_weight, the output and the bias are bf16 (include/mixq.h); any other type of A is the fp16 call
@@ -1270,34 +1248,18 @@ static int enqueue_impl(const mixq_handle* h, const mixq_tensor_desc* inputDesc,
         //  scattered 128-byte stores), prefill tokens/s -0.35 %: docs/LAB_NOTEBOOK.md R3.10.)
         const void* img = M <= 64 ? mixq::resolve_weight_image(W, (int)N, (int)K, st) : nullptr; // (ONE lookup per call: probe and launch agree)
         int frag = 0;
-        const mixq::GemmPlan plan = enqueue_plan(M, N, K, mixed_epi(bias != nullptr, bf16), scratch, img, &frag); // (ONE plan per call: quantiser and GEMM agree)
+        const mixq::GemmPlan plan = enqueue_plan(M, N, K, mixed_epi(bias != nullptr, bf16, 0), scratch, img, &frag); // (ONE plan per call: quantiser and GEMM agree)
         int rc = hip_rc(mixq::launch_quant_extract(const_cast<void*>(A), qA, sA, fpA, ind, (int)M, (int)K, kNumOutliers,
                                                    false, st, scratch, frag, bf16));
         if (rc != MIXQ_OK) return rc;
         if (ev_gemm_start && hipEventRecord(static_cast<hipEvent_t>(ev_gemm_start), st) != hipSuccess) return MIXQ_E_HIP;
-        rc = gemm_mixed_impl(qA, W, sA, scale_b, fpA, fp_weight, Out, (int)M, (int)N, (int)K, kNumOutliers, scratch,
-                             scratch_bytes, stream, frag, img, true, bias, bf16, &plan);
+        MixedCall c = mixed_call(qA, W, sA, scale_b, fpA, fp_weight, Out, (int)M, (int)N, (int)K, kNumOutliers, scratch, scratch_bytes, stream);
+        c.a_frag = frag, c.b_image = img, c.image_resolved = true, c.bias = bias, c.bf16 = bf16, c.plan = &plan;
+        rc = gemm_mixed_impl(c);
         if (ev_gemm_stop && hipEventRecord(static_cast<hipEvent_t>(ev_gemm_stop), st) != hipSuccess) return MIXQ_E_HIP;
         return rc;
     }
-    if (bf16) { // M <= 4 of a bf16 call: the same two forms as the fp16 call (the GEMV / the fpA_intB skinny form), bf16 twins
-        if (K % 64 || N % 2) return MIXQ_E_SHAPE;
-        if (!aligned16(A) || !aligned16(q_weight)) return MIXQ_E_ALIGN;
-        hipStream_t st = static_cast<hipStream_t>(stream);
-        if (!mixq::w8a16_skinny_takes((int)M, (int)N, (int)K))
-            return hip_rc(mixq::launch_w8a16_bf16(A, q_weight, scaling_factors, Out, (int)M, (int)N, (int)K, st, bias));
-        if (K % 8 || !w8a16_out_aligned(Out, (int)N)) return MIXQ_E_ALIGN;
-        return hip_rc(mixq::launch_w8a16_skinny_bf16(A, q_weight, scaling_factors, Out, (int)M, (int)N, (int)K, bias, st));
-    }
-    if (!bias) return mixq_w8a16_gemm_forward(A, q_weight, scaling_factors, Out, (int)M, (int)N, (int)K, stream);
-    // M <= 4 with the bias: the same two forms mixq_w8a16_gemm_forward picks from (the GEMV / the fpA_intB skinny form)
-    if (K % 64 || N % 2) return MIXQ_E_SHAPE;
-    if (!aligned16(A) || !aligned16(q_weight)) return MIXQ_E_ALIGN;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (!mixq::w8a16_skinny_takes((int)M, (int)N, (int)K))
-        return hip_rc(mixq::launch_w8a16(A, q_weight, scaling_factors, Out, (int)M, (int)N, (int)K, st, bias));
-    if (K % 8 || !w8a16_out_aligned(Out, (int)N)) return MIXQ_E_ALIGN;
-    return hip_rc(mixq::launch_w8a16_skinny_bias(A, q_weight, scaling_factors, Out, (int)M, (int)N, (int)K, bias, st));
+    return enqueue_small_m(A, q_weight, scaling_factors, Out, (int)M, (int)N, (int)K, bias, bf16, stream);
 }
 
 // The plan mixq_enqueue executes for a call with M rows on an [N, K] layer, as text (host only, no GPU needed; include/mixq.h).
