@@ -132,45 +132,58 @@ def _dev(*ts):
         assert t.is_contiguous(), "mixlib ops need contiguous tensors"
 
 
-def _p_dtype(what, x, **operands):
-    """The activation type of a P-flavour op: ``x``'s, fp16 or bf16 (MI355X extension).  The named operands (row scales, outliers,
-    outlier weights, outputs) must have it: a mixed call raises ``TypeError`` before anything reaches the library, which sees raw
-    pointers only."""
-    dt = x.dtype
-    if dt not in (torch.float16, torch.bfloat16):
-        raise TypeError(f"{what}: the activation is {dt}; fp16 and bf16 are supported")
+def _type_code(dt):
+    return _lib.MIXQ_TYPE_BF16 if dt == torch.bfloat16 else _lib.MIXQ_TYPE_HALF
+
+
+def _act_name(dtype):
+    return "bf16" if dtype == torch.bfloat16 else "fp16"
+
+
+_P_RULE = "is {got} in a {act} call"                                         # the P-flavour ops (TypeError)
+_P_FLOATS = "the activation is {dt}; fp16 and bf16 are supported"
+_NORM_RULE = "must be a {act} tensor like _input (got {got})"                # the norm ops (ValueError)
+
+
+def _same_dtype(exc, what, dt, rule, floats=None, **operands):
+    """The dtype rule of every op: each 16-bit operand (row scales, outliers, outlier weights, gamma, outputs ...) has the activation's
+    type ``dt``, fp16 or bf16 (MI355X extension).  A mixed call is refused before anything reaches the library, which sees raw pointers
+    only: the first named operand (None: not given) of another type raises ``exc`` -- the class its family has always raised,
+    ``ValueError`` for the norm ops, ``TypeError`` for the P-flavour ops and ``gemm_mixed`` -- with "what: name " + ``rule``.
+    ``floats``: the text that refuses a ``dt`` which is neither type (the norm ops have none: they run such a call as an fp16 call and
+    name ``_input``).  Returns ``dt``."""
+    if floats is not None and dt != torch.float16 and dt != torch.bfloat16:
+        raise exc(f"{what}: " + floats.format(dt=dt))
     for name, t in operands.items():
         if t is not None and t.dtype != dt:
-            raise TypeError(f"{what}: {name} is {t.dtype} in a {'bf16' if dt == torch.bfloat16 else 'fp16'} call")
+            raise exc(f"{what}: {name} " + rule.format(got=t.dtype, act=_act_name(dt)))
     return dt
 
 
-def _type_code(dt):
-    return _lib.MIXQ_TYPE_BF16 if dt == torch.bfloat16 else _lib.MIXQ_TYPE_HALF
+def _quant_rows(what, x, q, scaleRow, rows, cols, dt, outl=None, ind=None, len_ind=0, q_layout=QA_ROW_MAJOR):
+    """The row quantiser (``mixq_quant_extract_typed``) into ``q`` (int8 rows in ``q_layout``) and ``scaleRow``.  With ``outl``
+    [rows, len_ind] it is the extracting form: the columns ``ind`` are gathered there and zeroed in ``x`` first."""
+    _lib.check(_lib.load().mixq_quant_extract_typed(rows, cols, _p(x), _p(q), _p(scaleRow), _p(outl), _p(ind) if len_ind else None, len_ind,
+                                                    0 if outl is None else 1, q_layout, _type_code(dt), _st(x)), what)
 
 
 @_on_tensor_device
 def FindRowScale(x, scaleRow, rows, cols, bit=8):
     """cult.cu:2569-2608.  Writes the per-row scale into ``scaleRow`` and returns the int8 rows.  fp16, or (MI355X extension,
-    ``mixq_quant_extract_typed``, bit 8 only) bf16 ``x`` / ``scaleRow``: scale = bf16(amax / 127), q = sat(rint(x / scale))."""
-    dt = _p_dtype("FindRowScale", x, scaleRow=scaleRow)
+    bit 8 only) bf16 ``x`` / ``scaleRow``: scale = bf16(amax / 127), q = sat(rint(x / scale))."""
+    dt = _same_dtype(TypeError, "FindRowScale", x.dtype, _P_RULE, _P_FLOATS, scaleRow=scaleRow)
     if dt == torch.bfloat16 and bit != 8:
         raise TypeError("FindRowScale: there is no bf16 form of the packed 4-bit quantiser (bf16 rows take bit = 8)")
     _dev(x, scaleRow)
     _rows_fit(scaleRow, rows, "FindRowScale")
-    if dt == torch.bfloat16:
-        out = torch.empty((rows, cols), dtype=torch.int8, device=x.device)
-        _lib.check(_lib.load().mixq_quant_extract_typed(rows, cols, _p(x), _p(out), _p(scaleRow), None, None, 0, 0, QA_ROW_MAJOR,
-                                                        _lib.MIXQ_TYPE_BF16, _st(x)), "FindRowScale")
-        return out
-    if bit == 4:  # cult.cu:2588-2606: packed int4 pairs, scale = amax / 7
+    if bit == 4:  # cult.cu:2588-2606: packed int4 pairs, scale = amax / 7 (no typed entry: fp16 only)
         assert cols % 2 == 0
         out = torch.empty((rows, cols // 2), dtype=torch.uint8, device=x.device)
         _lib.check(_lib.load().mixq_int4quant(rows, cols, _p(x), _p(out), _p(scaleRow), _st(x)), "FindRowScale(4)")
         return out
     assert bit == 8
     out = torch.empty((rows, cols), dtype=torch.int8, device=x.device)
-    _lib.check(_lib.load().mixq_int8quant(rows, cols, _p(x), _p(out), _p(scaleRow), _st(x)), "FindRowScale")
+    _quant_rows("FindRowScale", x, out, scaleRow, rows, cols, dt)
     return out
 
 
@@ -178,7 +191,7 @@ def FindRowScale(x, scaleRow, rows, cols, bit=8):
 def ExtractOutliersAndSetToZeros(ind, input):
     """cult.cu:1433-1465.  Returns input[:, ind] ([M, len] of ``input``'s type, fp16 or bf16: a bit copy) and ZEROES those columns of
     ``input`` in place.  Every index lies in [0, K)."""
-    dt = _p_dtype("ExtractOutliersAndSetToZeros", input)
+    dt = _same_dtype(TypeError, "ExtractOutliersAndSetToZeros", input.dtype, _P_RULE, _P_FLOATS)
     _dev(ind, input)
     assert ind.dtype == torch.int32
     m, k = input.shape
@@ -222,16 +235,14 @@ def gemm_scratch(t, M, N, K):
 
 
 def _fused(name, A, B, scale_row, scale_col, y, M, N, K, qa_layout=0, epilogue=0, mul=None):
-    _dev(*(t for t in (A, B, scale_row, scale_col, y, mul) if t is not None))  # y = None: no addend (zeros in the reference)
+    """``mixq_int8_fused_dequantize_layout``: epilogue 0 (dequantise) | 1 (+ SiLU) | 3 (+ SiLU, * ``mul``); the exchange scratch goes
+    with a row-major ``A`` only (the fragment-major image has one reader, which takes none).  ``name``: the label of a ``MixQError``
+    (the two reference ops have always been labelled with their named fp16 entries)."""
+    _dev(*[t for t in (A, B, scale_row, scale_col, y, mul) if t is not None])  # y = None: no addend (zeros in the reference)
     D = torch.empty((M, N), dtype=torch.float16, device=A.device)
-    lib = _lib.load()
-    if qa_layout:   # the fragment-major image (decode batches): one entry for the three epilogues
-        _lib.check(lib.mixq_int8_fused_dequantize_layout(_p(A), _p(B), _p(scale_row), _p(scale_col), _p(y), _p(mul), _p(D), M, N,
-                                                         K, epilogue, qa_layout, None, _st(A)), name)
-        return D
-    fn = getattr(lib, name)
-    _lib.check(fn(_p(A), _p(B), _p(scale_row), _p(scale_col), _p(y), _p(D), M, N, K, _p(gemm_scratch(A, M, N, K)),
-                  _st(A)), name)
+    ws = None if qa_layout else gemm_scratch(A, M, N, K)
+    _lib.check(_lib.load().mixq_int8_fused_dequantize_layout(_p(A), _p(B), _p(scale_row), _p(scale_col), _p(y), _p(mul), _p(D), M, N, K,
+                                                             epilogue, qa_layout, _p(ws), _st(A)), name)
     return D
 
 
@@ -239,12 +250,14 @@ def _fused(name, A, B, scale_row, scale_col, y, M, N, K, qa_layout=0, epilogue=0
 def int8FusedDequantize(A, B, scale_row, scale_col, y, M, N, K, qa_layout=0):
     """cult.cu:1937-2000: D = fp16(float(A.B^T) * (scale_col[n]*scale_row[m]) + y), new tensor D.
     ``qa_layout`` (MI355X extension): the layout of ``A`` as its producer wrote it (``qa_layout()``); default row-major."""
+    # (the first argument is the label of a MixQError, kept as it always read; the call is mixq_int8_fused_dequantize_layout)
     return _fused("mixq_int8_fused_dequantize", A, B, scale_row, scale_col, y, M, N, K, qa_layout, 0)
 
 
 @_on_tensor_device
 def int8FusedDequantizeSilu(A, B, scale_row, scale_col, y, M, N, K, qa_layout=0):
     """cult.cu:2067-2117: same with SiLU applied before the fp16 rounding."""
+    # (a label, as above)
     return _fused("mixq_int8_fused_dequantize_silu", A, B, scale_row, scale_col, y, M, N, K, qa_layout, 1)
 
 
@@ -330,14 +343,7 @@ def unpack_int4_to_fp16(weight, ind):
 def int8FusedDequantizeSiluMul(A, B, scale_row, scale_col, y, mul, M, N, K, qa_layout=0):
     """MI355X extension (no reference op): int8FusedDequantizeSilu followed by ``*= mul`` (fused/mlp.py:61-63) in ONE
     kernel: D = fp16(fp16(silu(...)) * mul), the same bits as the two-step sequence."""
-    if qa_layout:
-        return _fused("int8FusedDequantizeSiluMul", A, B, scale_row, scale_col, y, M, N, K, qa_layout, 3, mul)
-    _dev(*(t for t in (A, B, scale_row, scale_col, y, mul) if t is not None))
-    D = torch.empty((M, N), dtype=torch.float16, device=A.device)
-    _lib.check(_lib.load().mixq_int8_fused_dequantize_silu_mul(_p(A), _p(B), _p(scale_row), _p(scale_col), _p(y), _p(mul),
-                                                              _p(D), M, N, K, _p(gemm_scratch(A, M, N, K)), _st(A)),
-               "int8FusedDequantizeSiluMul")
-    return D
+    return _fused("int8FusedDequantizeSiluMul", A, B, scale_row, scale_col, y, M, N, K, qa_layout, 3, mul)
 
 
 @_on_tensor_device
@@ -385,61 +391,80 @@ def Int8quantize(src, scale):
 def FindRowScaleFusedExtracOutliers(x, scaleRow, ind, len_ind, rows, cols, q_layout=0):
     """cult.cu:2671-2709: returns [int8 rows, outliers [rows,len_ind]]; zeroes the outlier columns of x.
     ``q_layout`` (MI355X extension): write the rows in the consumer's preferred image (``qa_layout()``).
-    fp16, or (MI355X extension, ``mixq_quant_extract_typed``) bf16 ``x`` / ``scaleRow`` with bf16 outliers: the bf16 quantiser on the
+    fp16, or (MI355X extension) bf16 ``x`` / ``scaleRow`` with bf16 outliers: the bf16 quantiser on the
     zeroed row; an index of -1 (the padding of a bf16 outlier set) gives a zero outlier column and zeroes nothing."""
-    dt = _p_dtype("FindRowScaleFusedExtracOutliers", x, scaleRow=scaleRow)
+    dt = _same_dtype(TypeError, "FindRowScaleFusedExtracOutliers", x.dtype, _P_RULE, _P_FLOATS, scaleRow=scaleRow)
     _dev(x, scaleRow)
     _rows_fit(scaleRow, rows, "FindRowScaleFusedExtracOutliers")
     q = _alloc_q(rows, cols, q_layout, x.device)
     outl = torch.empty((rows, len_ind), dtype=dt, device=x.device)
-    if dt == torch.bfloat16:
-        _lib.check(_lib.load().mixq_quant_extract_typed(rows, cols, _p(x), _p(q), _p(scaleRow), _p(outl), _p(ind) if len_ind else None,
-                                                        len_ind, 1, q_layout, _lib.MIXQ_TYPE_BF16, _st(x)),
-                   "FindRowScaleFusedExtracOutliers")
-        return [q, outl]
-    _lib.check(_lib.load().mixq_quant_extract_layout(rows, cols, _p(x), _p(q), _p(scaleRow), _p(outl),
-                                                     _p(ind) if len_ind else None, len_ind, 1, q_layout, _st(x)),
-               "FindRowScaleFusedExtracOutliers")
+    _quant_rows("FindRowScaleFusedExtracOutliers", x, q, scaleRow, rows, cols, dt, outl, ind, len_ind, q_layout)
     return [q, outl]
 
 
-def _act_dtype(_input):
-    """The activation type a norm op runs in: bf16 for a bf16 ``_input`` (MI355X extension), else the reference's fp16."""
-    return torch.bfloat16 if _input.dtype == torch.bfloat16 else torch.float16
-
-
-def _act_name(dtype):
-    return "bf16" if dtype == torch.bfloat16 else "fp16"
-
-
-def _same_dtype(what, dtype, **operands):
-    """gamma, the outputs and the row scales of a norm op have ``_input``'s type: checked before anything reaches the library,
-    which sees raw pointers only."""
-    for name, t in operands.items():
-        if t is not None and t.dtype != dtype:
-            raise ValueError(f"{what}: {name} must be a {_act_name(dtype)} tensor like _input (got {t.dtype})")
-
-
-def _no_bf16_int4(what, _input):
-    if _input.dtype == torch.bfloat16:
+def _norm(what, _input, _residual, h_out, _gamma, _out, eps, quant=0, _ind=None, scaleRow=None, q_layout=0):
+    """The six norm ops: RMSNorm of ``_input`` -- with ``_residual``, of h = _input + _residual, written to ``h_out`` (None: in place
+    into ``_residual``) in the same pass -- into ``_out``; ``quant`` 8 | 4 also gathers (and zeroes in ``_out``) the columns ``_ind`` and
+    quantises the row to int8 (in ``q_layout``) | packed 4-bit pairs, scales to ``scaleRow``.  bf16 for a bf16 ``_input`` (MI355X
+    extension; quant 0 | 8: ``mixq_rmsnorm_typed`` / ``mixq_rmsnorm_extract_quant_typed``), else the reference's fp16; the 4-bit producer
+    has no typed entry and is fp16 only.  Returns (h, [outliers, quant]), either None where the op has none."""
+    if quant == 4 and _input.dtype == torch.bfloat16:
         raise TypeError(f"{what}: there is no bf16 form of the packed 4-bit producer (fp16 tensors only)")
+    dt = torch.bfloat16 if _input.dtype == torch.bfloat16 else torch.float16
+    if _residual is None:
+        h = None
+        if quant != 4:
+            _same_dtype(ValueError, what, dt, _NORM_RULE, _input=_input, _gamma=_gamma, _out=_out, scaleRow=scaleRow)
+    else:   # the row operands: ``_input``'s type, contiguous, and its shape
+        h = _residual if h_out is None else h_out
+        for name, t in (("_input", _input), ("_residual", _residual), ("h_out", h)):
+            if t.dtype != dt or not t.is_contiguous():
+                raise ValueError(f"{what}: {name} must be a contiguous {_act_name(dt)} tensor (got {t.dtype}, contiguous={t.is_contiguous()})")
+            if t.shape != _input.shape:
+                raise ValueError(f"{what}: {name} has shape {tuple(t.shape)}, _input has {tuple(_input.shape)}")
+        if quant != 4:
+            _same_dtype(ValueError, what, dt, _NORM_RULE, _gamma=_gamma, _out=_out, scaleRow=scaleRow)
+    if h is None:
+        res = hp = None
+        if quant:
+            _dev(_input, _gamma, _out, _ind, scaleRow)
+        else:
+            _dev(_input, _gamma, _out)
+    else:
+        res, hp = _residual.data_ptr(), h.data_ptr()
+        if quant:
+            _dev(_input, _residual, h, _gamma, _out, _ind, scaleRow)
+        else:
+            _dev(_input, _residual, h, _gamma, _out)
+    c = _input.shape[-1]
+    m = _input.numel() // c
+    lib = _lib.load()
+    x, e, st = _input.data_ptr(), ctypes.c_float(eps), _st(_input)
+    if not quant:
+        _lib.check(lib.mixq_rmsnorm_typed(m, c, x, res, hp, _p(_gamma), _p(_out), e, _type_code(dt), st), what)
+        return h, None
+    _rows_fit(scaleRow, m, what)
+    n = _ind.shape[0]
+    outl = torch.zeros((m, n), dtype=dt, device=_input.device)
+    if quant == 8:
+        q = _alloc_q(m, c, q_layout, _input.device)
+        rc = lib.mixq_rmsnorm_extract_quant_typed(m, c, x, res, hp, _p(_gamma), _p(_out), e, _p(_ind), n, _p(outl), _p(q), _p(scaleRow),
+                                                  q_layout, _type_code(dt), st)
+    else:
+        q = torch.empty((m, c // 2), dtype=torch.uint8, device=_input.device)
+        if h is None:
+            rc = lib.mixq_rmsnorm_extract_quant4(m, c, x, _p(_gamma), _p(_out), e, _p(_ind), n, _p(outl), _p(q), _p(scaleRow), st)
+        else:
+            rc = lib.mixq_add_rmsnorm_extract_quant4(m, c, x, res, hp, _p(_gamma), _p(_out), e, _p(_ind), n, _p(outl), _p(q), _p(scaleRow), st)
+    _lib.check(rc, what)
+    return h, [outl, q]
 
 
 @_on_tensor_device
 def layernorm_forward_cuda(_input, _gamma, _out, eps):
     """layernorm.cu:100-117: T5-style RMSNorm of _input [b, n, c] (or [m, c]) into _out.
-    A bf16 ``_input`` (MI355X extension, ``mixq_rmsnorm_typed``) takes bf16 ``_gamma`` / ``_out``."""
-    dt = _act_dtype(_input)
-    _same_dtype("layernorm_forward_cuda", dt, _input=_input, _gamma=_gamma, _out=_out)
-    _dev(_input, _gamma, _out)
-    c = _input.shape[-1]
-    m = _input.numel() // c
-    if dt == torch.bfloat16:
-        _lib.check(_lib.load().mixq_rmsnorm_typed(m, c, _p(_input), None, None, _p(_gamma), _p(_out), ctypes.c_float(eps),
-                                                  _lib.MIXQ_TYPE_BF16, _st(_input)), "layernorm_forward_cuda")
-        return
-    _lib.check(_lib.load().mixq_rmsnorm(m, c, _p(_input), _p(_gamma), _p(_out), ctypes.c_float(eps), _st(_input)),
-               "layernorm_forward_cuda")
+    A bf16 ``_input`` (MI355X extension) takes bf16 ``_gamma`` / ``_out``."""
+    _norm("layernorm_forward_cuda", _input, None, None, _gamma, _out, eps)
 
 
 @_on_tensor_device
@@ -447,133 +472,45 @@ def layernorm_forward_cuda_extract_outliers(_input, _gamma, _out, eps, _ind, sca
     """layernorm.cu:316-346: fused RMSNorm -> extract(+zero) outliers -> per-row int8 quantisation.
     Fills _out (normalised, outlier columns zeroed) and scaleRow; returns [outliers fp16 [m,len], quant int8 [m,c]].
     ``q_layout`` (MI355X extension): write the int8 rows in the consumer's preferred image (``qa_layout()``).
-    A bf16 ``_input`` (MI355X extension, ``mixq_rmsnorm_extract_quant_typed``) takes bf16 ``_gamma`` / ``_out`` / ``scaleRow`` and
+    A bf16 ``_input`` (MI355X extension) takes bf16 ``_gamma`` / ``_out`` / ``scaleRow`` and
     returns bf16 outliers; the int8 rows follow the bf16 quantiser's rules (scale = bf16(amax / 127), no fp16 quotient)."""
-    dt = _act_dtype(_input)
-    _same_dtype("layernorm_forward_cuda_extract_outliers", dt, _input=_input, _gamma=_gamma, _out=_out, scaleRow=scaleRow)
-    _dev(_input, _gamma, _out, _ind, scaleRow)
-    c = _input.shape[-1]
-    m = _input.numel() // c
-    _rows_fit(scaleRow, m, "layernorm_forward_cuda_extract_outliers")
-    n = _ind.shape[0]
-    outl = torch.zeros((m, n), dtype=dt, device=_input.device)
-    q = _alloc_q(m, c, q_layout, _input.device)
-    if dt == torch.bfloat16:
-        _lib.check(_lib.load().mixq_rmsnorm_extract_quant_typed(m, c, _p(_input), None, None, _p(_gamma), _p(_out), ctypes.c_float(eps),
-                                                                _p(_ind), n, _p(outl), _p(q), _p(scaleRow), q_layout,
-                                                                _lib.MIXQ_TYPE_BF16, _st(_input)),
-                   "layernorm_forward_cuda_extract_outliers")
-        return [outl, q]
-    _lib.check(_lib.load().mixq_rmsnorm_extract_quant_layout(m, c, _p(_input), _p(_gamma), _p(_out), ctypes.c_float(eps),
-                                                             _p(_ind), n, _p(outl), _p(q), _p(scaleRow), q_layout,
-                                                             _st(_input)),
-               "layernorm_forward_cuda_extract_outliers")
-    return [outl, q]
+    return _norm("layernorm_forward_cuda_extract_outliers", _input, None, None, _gamma, _out, eps, 8, _ind, scaleRow, q_layout)[1]
 
 
 @_on_tensor_device
 def layernorm_forward_cuda_extract_outliers_int4(_input, _gamma, _out, eps, _ind, scaleRow):
     """layernorm.cu:379-414: the same fused producer with packed 4-bit rows (scale = amax / 7).
     Returns [outliers fp16 [m,len], quant uint8 [m, c/2]].  fp16 only: a bf16 ``_input`` raises ``TypeError``."""
-    _no_bf16_int4("layernorm_forward_cuda_extract_outliers_int4", _input)
-    _dev(_input, _gamma, _out, _ind, scaleRow)
-    c = _input.shape[-1]
-    m = _input.numel() // c
-    _rows_fit(scaleRow, m, "layernorm_forward_cuda_extract_outliers_int4")
-    n = _ind.shape[0]
-    outl = torch.zeros((m, n), dtype=torch.float16, device=_input.device)
-    q = torch.empty((m, c // 2), dtype=torch.uint8, device=_input.device)
-    _lib.check(_lib.load().mixq_rmsnorm_extract_quant4(m, c, _p(_input), _p(_gamma), _p(_out), ctypes.c_float(eps),
-                                                       _p(_ind), n, _p(outl), _p(q), _p(scaleRow), _st(_input)),
-               "layernorm_forward_cuda_extract_outliers_int4")
-    return [outl, q]
-
-
-def _add_operands(_input, _residual, h_out, what):
-    """The residual-add forms' row operands: same shape, ``_input``'s type (fp16, or bf16 for a bf16 ``_input``), contiguous;
-    ``h_out`` None = in place into ``_residual``."""
-    h = _residual if h_out is None else h_out
-    dt = _act_dtype(_input)
-    for name, t in (("_input", _input), ("_residual", _residual), ("h_out", h)):
-        if t.dtype != dt or not t.is_contiguous():
-            raise ValueError(f"{what}: {name} must be a contiguous {_act_name(dt)} tensor (got {t.dtype}, contiguous={t.is_contiguous()})")
-        if t.shape != _input.shape:
-            raise ValueError(f"{what}: {name} has shape {tuple(t.shape)}, _input has {tuple(_input.shape)}")
-    return h
+    return _norm("layernorm_forward_cuda_extract_outliers_int4", _input, None, None, _gamma, _out, eps, 4, _ind, scaleRow)[1]
 
 
 @_on_tensor_device
 def add_layernorm_forward_cuda(_input, _residual, _gamma, _out, eps, h_out=None):
-    """MI355X extension (``mixq_add_rmsnorm``): ``layernorm_forward_cuda`` on h = _input + _residual (fp16, rounded once) in one
+    """MI355X extension: ``layernorm_forward_cuda`` on h = _input + _residual (rounded once to the call's type: torch's add) in one
     pass; h goes to ``h_out`` (None: in place into ``_residual``; it may also be ``_input``) and is returned.  Same bits as the
     torch add followed by ``layernorm_forward_cuda``."""
-    h = _add_operands(_input, _residual, h_out, "add_layernorm_forward_cuda")
-    dt = _act_dtype(_input)
-    _same_dtype("add_layernorm_forward_cuda", dt, _gamma=_gamma, _out=_out)
-    _dev(_input, _residual, h, _gamma, _out)
-    c = _input.shape[-1]
-    m = _input.numel() // c
-    if dt == torch.bfloat16:   # (``mixq_rmsnorm_typed``: h = bf16(_input + _residual), torch's bf16 add)
-        _lib.check(_lib.load().mixq_rmsnorm_typed(m, c, _p(_input), _p(_residual), _p(h), _p(_gamma), _p(_out), ctypes.c_float(eps),
-                                                  _lib.MIXQ_TYPE_BF16, _st(_input)), "add_layernorm_forward_cuda")
-        return h
-    _lib.check(_lib.load().mixq_add_rmsnorm(m, c, _p(_input), _p(_residual), _p(h), _p(_gamma), _p(_out), ctypes.c_float(eps),
-                                            _st(_input)), "add_layernorm_forward_cuda")
-    return h
+    return _norm("add_layernorm_forward_cuda", _input, _residual, h_out, _gamma, _out, eps)[0]
 
 
 @_on_tensor_device
 def add_layernorm_forward_cuda_extract_outliers(_input, _residual, _gamma, _out, eps, _ind, scaleRow, q_layout=0, h_out=None):
-    """MI355X extension (``mixq_add_rmsnorm_extract_quant_layout``): ``layernorm_forward_cuda_extract_outliers`` on
+    """MI355X extension: ``layernorm_forward_cuda_extract_outliers`` on
     h = _input + _residual in one pass; h goes to ``h_out`` (None: in place into ``_residual``).  Returns [outliers, quant]."""
-    h = _add_operands(_input, _residual, h_out, "add_layernorm_forward_cuda_extract_outliers")
-    dt = _act_dtype(_input)
-    _same_dtype("add_layernorm_forward_cuda_extract_outliers", dt, _gamma=_gamma, _out=_out, scaleRow=scaleRow)
-    _dev(_input, _residual, h, _gamma, _out, _ind, scaleRow)
-    c = _input.shape[-1]
-    m = _input.numel() // c
-    _rows_fit(scaleRow, m, "add_layernorm_forward_cuda_extract_outliers")
-    n = _ind.shape[0]
-    outl = torch.zeros((m, n), dtype=dt, device=_input.device)
-    q = _alloc_q(m, c, q_layout, _input.device)
-    if dt == torch.bfloat16:   # (``mixq_rmsnorm_extract_quant_typed``)
-        _lib.check(_lib.load().mixq_rmsnorm_extract_quant_typed(m, c, _p(_input), _p(_residual), _p(h), _p(_gamma), _p(_out),
-                                                                ctypes.c_float(eps), _p(_ind), n, _p(outl), _p(q), _p(scaleRow), q_layout,
-                                                                _lib.MIXQ_TYPE_BF16, _st(_input)),
-                   "add_layernorm_forward_cuda_extract_outliers")
-        return [outl, q]
-    _lib.check(_lib.load().mixq_add_rmsnorm_extract_quant_layout(m, c, _p(_input), _p(_residual), _p(h), _p(_gamma), _p(_out),
-                                                                 ctypes.c_float(eps), _p(_ind), n, _p(outl), _p(q), _p(scaleRow),
-                                                                 q_layout, _st(_input)),
-               "add_layernorm_forward_cuda_extract_outliers")
-    return [outl, q]
+    return _norm("add_layernorm_forward_cuda_extract_outliers", _input, _residual, h_out, _gamma, _out, eps, 8, _ind, scaleRow, q_layout)[1]
 
 
 @_on_tensor_device
 def add_layernorm_forward_cuda_extract_outliers_int4(_input, _residual, _gamma, _out, eps, _ind, scaleRow, h_out=None):
     """MI355X extension (``mixq_add_rmsnorm_extract_quant4``): the same with packed 4-bit rows (scale = amax / 7).
     Returns [outliers fp16 [m,len], quant uint8 [m, c/2]].  fp16 only: a bf16 ``_input`` raises ``TypeError``."""
-    _no_bf16_int4("add_layernorm_forward_cuda_extract_outliers_int4", _input)
-    h = _add_operands(_input, _residual, h_out, "add_layernorm_forward_cuda_extract_outliers_int4")
-    _dev(_input, _residual, h, _gamma, _out, _ind, scaleRow)
-    c = _input.shape[-1]
-    m = _input.numel() // c
-    _rows_fit(scaleRow, m, "add_layernorm_forward_cuda_extract_outliers_int4")
-    n = _ind.shape[0]
-    outl = torch.zeros((m, n), dtype=torch.float16, device=_input.device)
-    q = torch.empty((m, c // 2), dtype=torch.uint8, device=_input.device)
-    _lib.check(_lib.load().mixq_add_rmsnorm_extract_quant4(m, c, _p(_input), _p(_residual), _p(h), _p(_gamma), _p(_out),
-                                                           ctypes.c_float(eps), _p(_ind), n, _p(outl), _p(q), _p(scaleRow),
-                                                           _st(_input)),
-               "add_layernorm_forward_cuda_extract_outliers_int4")
-    return [outl, q]
+    return _norm("add_layernorm_forward_cuda_extract_outliers_int4", _input, _residual, h_out, _gamma, _out, eps, 4, _ind, scaleRow)[1]
 
 
 @_on_tensor_device
 def ExtractOutliers(ind, input):
     """cult.cu ExtractOutliers: input[:, ind] as [M, len] of ``input``'s type (fp16 or bf16: a bit copy); `input` is left untouched
     (T-flavour gather)."""
-    dt = _p_dtype("ExtractOutliers", input)
+    dt = _same_dtype(TypeError, "ExtractOutliers", input.dtype, _P_RULE, _P_FLOATS)
     _dev(ind, input)
     m, k = input.shape
     n = ind.shape[0]
@@ -675,44 +612,41 @@ def gemm_mixed(q, W_int8, x_scale, sW, outliers, fp_weight, M, N, K, bias=None, 
     if act is not None and bias is not None:
         raise ValueError("gemm_mixed: the SiLU epilogues take no bias")
     O = 0 if outliers is None else int(outliers.shape[-1])
-    dt = outliers.dtype if O else x_scale.dtype
-    if dt not in (torch.float16, torch.bfloat16):
-        raise TypeError(f"gemm_mixed: the activation type is {dt}; fp16 and bf16 are supported")
-    for name, t in (("x_scale", x_scale), ("fp_weight", fp_weight if O else None), ("bias", bias), ("out", out), ("mul", mul)):
-        if t is not None and t.dtype != dt:
-            raise TypeError(f"gemm_mixed: {name} is {t.dtype} in a {_act_name(dt)} call (x_scale, outliers, fp_weight, bias, mul and out share one type)")
+    dt = _same_dtype(TypeError, "gemm_mixed", outliers.dtype if O else x_scale.dtype,
+                     "is {got} in a {act} call (x_scale, outliers, fp_weight, bias, mul and out share one type)",
+                     "the activation type is {dt}; fp16 and bf16 are supported",
+                     x_scale=x_scale, fp_weight=fp_weight if O else None, bias=bias, out=out, mul=mul)
     if mul is not None and (mul.numel() != M * N or mul is out or (out is not None and mul.data_ptr() == out.data_ptr())):
         raise ValueError(f"gemm_mixed: mul holds {mul.numel()} elements ({M} x {N} needed) and must not be out")
     if sW.dtype != torch.float16 or q.dtype != torch.int8 or W_int8.dtype != torch.int8:
         raise TypeError("gemm_mixed: q and W_int8 are int8, sW is fp16")
-    _dev(*(t for t in (q, W_int8, x_scale, sW, outliers if O else None, fp_weight if O else None, bias, out, mul) if t is not None))
+    _dev(*[t for t in (q, W_int8, x_scale, sW, outliers if O else None, fp_weight if O else None, bias, out, mul) if t is not None])
     _rows_fit(x_scale, M, "gemm_mixed")
     if out is None:
         out = torch.empty((M, N), dtype=dt, device=q.device)
     assert out.numel() == M * N and (bias is None or bias.numel() == N) and sW.numel() >= N
     scr = None if qa_layout else gemm_scratch(q, M, N, K)
-    if act is not None:
-        _lib.check(_lib.load().mixq_gemm_mixed_act_typed(_p(q), _p(W_int8), _p(x_scale), _p(sW), _p(outliers) if O else None,
-                                                         _p(fp_weight) if O else None, _p(mul), _p(out), M, N, K, O, 1 if mul is None else 3,
-                                                         qa_layout, _lib.MIXQ_TYPE_BF16 if dt == torch.bfloat16 else _lib.MIXQ_TYPE_HALF,
-                                                         _p(scr), scr.numel() if scr is not None else 0, _st(q)), "gemm_mixed")
-        return out
-    _lib.check(_lib.load().mixq_gemm_mixed_typed(_p(q), _p(W_int8), _p(x_scale), _p(sW), _p(outliers) if O else None,
-                                                 _p(fp_weight) if O else None, _p(bias), _p(out), M, N, K, O, qa_layout,
-                                                 _lib.MIXQ_TYPE_BF16 if dt == torch.bfloat16 else _lib.MIXQ_TYPE_HALF, _p(scr),
-                                                 scr.numel() if scr is not None else 0, _st(q)), "gemm_mixed")
+    lib = _lib.load()
+    operands = (_p(q), _p(W_int8), _p(x_scale), _p(sW), _p(outliers) if O else None, _p(fp_weight) if O else None)
+    rest = (qa_layout, _type_code(dt), _p(scr), scr.numel() if scr is not None else 0, _st(q))
+    if act is not None:   # (bias and act are separate entries in C)
+        rc = lib.mixq_gemm_mixed_act_typed(*operands, _p(mul), _p(out), M, N, K, O, 1 if mul is None else 3, *rest)
+    else:
+        rc = lib.mixq_gemm_mixed_typed(*operands, _p(bias), _p(out), M, N, K, O, *rest)
+    _lib.check(rc, "gemm_mixed")
     return out
 
 
 @_on_tensor_device
 def mixlinear_forward(x, ind, q_weight, scale_col, weight_cache, x_scale, q_layout=0):
     """MixLinear_GEMM.forward (linear.py:163-286, bit = 8, static outlier set) in ONE library call and two launches (MI355X
-    extension, include/mixq.h ``mixq_mixlinear_forward``): returns (out [M,N], q_x int8 [M,K], outliers [M,O]); zeroes
+    extension, include/mixq.h ``mixq_mixlinear_forward_typed``): returns (out [M,N], q_x int8 [M,K], outliers [M,O]); zeroes
     the ``ind`` columns of ``x`` and fills ``x_scale`` like the reference's four-call sequence.  The wrapper does what one of
     the four wrappers does -- the host cost per linear drops ~4x (profiles/r03_mixlib_overhead.txt).
-    fp16, or (``mixq_mixlinear_forward_typed``) bf16 ``x`` / ``weight_cache`` / ``x_scale`` with bf16 results; ``scale_col`` stays
+    fp16, or bf16 ``x`` / ``weight_cache`` / ``x_scale`` with bf16 results; ``scale_col`` stays
     fp16.  A bf16 call takes a multiple of 8 and at most 128 outlier columns, -1 entries of ``ind`` being zero columns."""
-    dt = _p_dtype("mixlinear_forward", x, x_scale=x_scale, weight_cache=weight_cache if ind.shape[0] else None)
+    dt = _same_dtype(TypeError, "mixlinear_forward", x.dtype, _P_RULE, _P_FLOATS, x_scale=x_scale,
+                     weight_cache=weight_cache if ind.shape[0] else None)
     if scale_col.dtype != torch.float16:
         raise TypeError(f"mixlinear_forward: scale_col is {scale_col.dtype}; the weight scales stay fp16 in either type")
     _dev(x, ind, q_weight, scale_col, x_scale)   # (the same guards as the four wrappers this call replaces: raw pointers go to C)
@@ -731,18 +665,9 @@ def mixlinear_forward(x, ind, q_weight, scale_col, weight_cache, x_scale, q_layo
     outliers = torch.empty((M, O), dtype=dt, device=dev)
     lib = _lib.load()
     scratch = None if q_layout else gemm_scratch(x, M, N, K)
-    if dt == torch.bfloat16:
-        _lib.check(lib.mixq_mixlinear_forward_typed(M, N, K, O, x.data_ptr(), ind.data_ptr() if O else None, q_weight.data_ptr(),
-                                                    scale_col.data_ptr(), weight_cache.data_ptr() if (O and weight_cache is not None) else None,
-                                                    x_scale.data_ptr(), q_x.data_ptr(), outliers.data_ptr() if O else None, out.data_ptr(),
-                                                    q_layout, _lib.MIXQ_TYPE_BF16, scratch.data_ptr() if scratch is not None else None,
-                                                    scratch.numel() if scratch is not None else 0, _st(x)), "mixlinear_forward")
-        return out, q_x, outliers
-    _lib.check(lib.mixq_mixlinear_forward(M, N, K, O, x.data_ptr(), ind.data_ptr() if O else None, q_weight.data_ptr(),
-                                          scale_col.data_ptr(), weight_cache.data_ptr() if (O and weight_cache is not None) else None,
-                                          x_scale.data_ptr(),
-                                          q_x.data_ptr(), outliers.data_ptr() if O else None, out.data_ptr(), q_layout,
-                                          scratch.data_ptr() if scratch is not None else None,
-                                          scratch.numel() if scratch is not None else 0,
-                                          _st(x)), "mixlinear_forward")
+    _lib.check(lib.mixq_mixlinear_forward_typed(M, N, K, O, x.data_ptr(), ind.data_ptr() if O else None, q_weight.data_ptr(),
+                                                scale_col.data_ptr(), weight_cache.data_ptr() if (O and weight_cache is not None) else None,
+                                                x_scale.data_ptr(), q_x.data_ptr(), outliers.data_ptr() if O else None, out.data_ptr(),
+                                                q_layout, _type_code(dt), scratch.data_ptr() if scratch is not None else None,
+                                                scratch.numel() if scratch is not None else 0, _st(x)), "mixlinear_forward")
     return out, q_x, outliers

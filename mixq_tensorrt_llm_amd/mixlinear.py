@@ -8,7 +8,7 @@ found, moved out of the int8 path (zeroed in the activation, their weights dequa
 rows are re-quantised.  The product is  fp16(float(qA . qW^T) * (scale_col * x_scale) + outliers . weight_cache^T).
 
 Every tensor op of the forward is a launch of libmixq_mi355x.so (no torch.mm / torch.where / torch.unique on the data
-path): FindOutliers -> `mixq_find_outliers`, weight_cache columns -> `mixq_dequant_weight_columns`, the outlier product
+path): FindOutliers -> `mixq_find_outliers_typed`, weight_cache columns -> `mixq_dequant_weight_columns_typed`, the outlier product
 -> `mixq_gemm_fp16`, the rest are the mixlib ops.  torch is used for allocation, `hstack` of the growing state and the
 quantize-time `from_linear` (like the reference).  bit = 8 and bit = 4 (W4A4: packed int4 storage, sign-extended to
 int8 for the MFMA kernels -- gfx950 has no int4 matrix instruction) and the weight-only W8A16 mode.
@@ -29,8 +29,8 @@ from .mixlib import _p, _st  # noqa: E402  (raw pointers / the raw current strea
 
 def find_outliers(activation: torch.Tensor, sigma: float, capacity: int = None) -> torch.Tensor:
     """linear.py:155-161 ``torch.unique(torch.where(A.abs() > sigma)[1]).to(int32)``: ascending column indices.
-    fp16 or (MI355X extension, ``mixq_find_outliers_typed``) bf16 rows, compared in fp32 as torch does against an fp16 sigma."""
-    dt = mixlib._p_dtype("find_outliers", activation)
+    fp16 or (MI355X extension) bf16 rows, compared in fp32 as torch does against an fp16 sigma."""
+    dt = mixlib._same_dtype(TypeError, "find_outliers", activation.dtype, mixlib._P_RULE, mixlib._P_FLOATS)
     assert activation.is_cuda and activation.dim() == 2
     a = activation.contiguous()
     m, k = a.shape
@@ -39,12 +39,8 @@ def find_outliers(activation: torch.Tensor, sigma: float, capacity: int = None) 
     ws = torch.empty((lib.mixq_find_outliers_workspace_size(k) + 3) // 4, dtype=torch.int32, device=a.device)
     ind = torch.empty(cap, dtype=torch.int32, device=a.device)
     cnt = torch.zeros(1, dtype=torch.int32, device=a.device)
-    if dt == torch.bfloat16:
-        _lib.check(lib.mixq_find_outliers_typed(_p(a), m, k, ctypes.c_float(float(sigma)), _p(ws), _p(ind), _p(cnt), cap,
-                                                _lib.MIXQ_TYPE_BF16, _st(a)), "find_outliers")
-    else:
-        _lib.check(lib.mixq_find_outliers(_p(a), m, k, ctypes.c_float(float(sigma)), _p(ws), _p(ind), _p(cnt), cap, _st(a)),
-                   "find_outliers")
+    _lib.check(lib.mixq_find_outliers_typed(_p(a), m, k, ctypes.c_float(float(sigma)), _p(ws), _p(ind), _p(cnt), cap,
+                                            mixlib._type_code(dt), _st(a)), "find_outliers")
     n = int(cnt.item())  # the reference's torch.unique synchronises too (data-dependent output size)
     return ind[: min(n, cap)]
 
@@ -52,7 +48,7 @@ def find_outliers(activation: torch.Tensor, sigma: float, capacity: int = None) 
 def dequant_weight_columns(q_weight: torch.Tensor, scale_col: torch.Tensor, ind: torch.Tensor,
                            dtype=torch.float16) -> torch.Tensor:
     """linear.py:207-209 ``q_weight[:, ind].to(float16) * scale_col.T`` -> fp16 [N, len(ind)].
-    ``dtype=torch.bfloat16`` (MI355X extension, ``mixq_dequant_weight_columns_typed``): bf16(fp32(q) * fp32(scale)), one rounding;
+    ``dtype=torch.bfloat16`` (MI355X extension): bf16(fp32(q) * fp32(scale)), one rounding;
     ``scale_col`` stays fp16; an index outside [0, K) (the -1 padding of a bf16 outlier set) gives a zero column."""
     if dtype not in (torch.float16, torch.bfloat16):
         raise TypeError(f"dequant_weight_columns: dtype is {dtype}; fp16 and bf16 are supported")
@@ -61,12 +57,8 @@ def dequant_weight_columns(q_weight: torch.Tensor, scale_col: torch.Tensor, ind:
     assert q_weight.is_cuda and q_weight.dtype == torch.int8 and ind.dtype == torch.int32
     n, k = q_weight.shape
     out = torch.empty((n, ind.shape[0]), dtype=dtype, device=q_weight.device)
-    if dtype == torch.bfloat16:
-        _lib.check(_lib.load().mixq_dequant_weight_columns_typed(_p(q_weight), _p(scale_col), _p(ind), ind.shape[0], _p(out), n, k,
-                                                                 _lib.MIXQ_TYPE_BF16, _st(q_weight)), "dequant_weight_columns")
-        return out
-    _lib.check(_lib.load().mixq_dequant_weight_columns(_p(q_weight), _p(scale_col), _p(ind), ind.shape[0], _p(out), n,
-                                                       k, _st(q_weight)), "dequant_weight_columns")
+    _lib.check(_lib.load().mixq_dequant_weight_columns_typed(_p(q_weight), _p(scale_col), _p(ind), ind.shape[0], _p(out), n, k,
+                                                             mixlib._type_code(dtype), _st(q_weight)), "dequant_weight_columns")
     return out
 
 
@@ -258,20 +250,8 @@ class MixLinear_GEMM:
             return y.reshape(cache.shape)
 
         if unfused and self.bit == 8 and not self.add_outliers and inputs.is_contiguous():
-            # static outlier set: the reference's four mixlib calls (:186-189, :241-247) as ONE library call and two launches
-            # (mixq_mixlinear_forward); a decode step is host-bound on those calls long before it is GPU-bound
-            # (profiles/r03_mixlib_overhead.txt: 42.6 us of host time per linear through four wrappers, 16 us as four direct
-            # C-ABI calls, 7.8 us as this one)
             assert cache.x_scale.numel() >= M
-            cache.ind = self.ind
-            wc = self.weight_cache if self.ind.shape[0] else None
-            n_out = int(self.ind.shape[0])
-            cache.q_layout = mixlib.qa_layout(M, self.out_features, self.in_features) if (n_out % 8 == 0 and n_out <= 128) else 0
-            y1, cache.q_xcache, cache.activation_outliers = mixlib.mixlinear_forward(
-                inputs, self.ind, self.q_weight, self.scale_col, wc, cache.x_scale, cache.q_layout)
-            if self.bias is not None:
-                y1 += self.bias
-            return y1.reshape(cache.shape)
+            return self._forward_static(inputs, cache, M)
         if unfused:
             if self.ind.shape[0]:
                 cache.activation_outliers = mixlib.ExtractOutliersAndSetToZeros(self.ind, inputs)
@@ -285,16 +265,11 @@ class MixLinear_GEMM:
                 ind = self.FindOutliers(inputs)
                 cache.new_ind = ind
                 activation_outliers = mixlib.ExtractOutliersAndSetToZeros(ind, inputs)
-                if self.bit == 8:
-                    weight_cache = dequant_weight_columns(self.q_weight, self.scale_col, ind)
-                else:  # :210-212 (fp16 x fp16 product, like the reference's tensor expression)
-                    weight_cache = mixlib.unpack_int4_to_fp16(self.q_weight, ind) * self.scale_col.T
+                self._adopt_weight_columns(ind)
                 if self.ind.shape[0] == 0:
                     cache.activation_outliers = activation_outliers
-                    self.weight_cache = weight_cache
                 else:
                     cache.activation_outliers = torch.hstack((cache.activation_outliers, activation_outliers))
-                    self.weight_cache = torch.hstack((self.weight_cache, weight_cache))
                 self.ind = torch.hstack((self.ind, ind))
                 cache.ind = self.ind
                 cache.q_xcache = mixlib.FindRowScale(inputs, cache.x_scale, M, self.in_features, self.bit)
@@ -319,6 +294,28 @@ class MixLinear_GEMM:
         return y1.reshape(cache.shape)
 
     __call__ = forward
+
+    def _forward_static(self, inputs, cache, M):
+        """A static outlier set on unquantised rows: the reference's four mixlib calls (:186-189, :241-247) as ONE library call and
+        two launches (``mixlib.mixlinear_forward``); a decode step is host-bound on those calls long before it is GPU-bound
+        (profiles/r03_mixlib_overhead.txt: 42.6 us of host time per linear through four wrappers, 16 us as four direct C-ABI calls,
+        7.8 us as this one).  Leaves ind / q_xcache / q_layout / activation_outliers in the cache like the sequence does."""
+        cache.ind = self.ind
+        n_out = int(self.ind.shape[0])
+        cache.q_layout = mixlib.qa_layout(M, self.out_features, self.in_features) if (n_out % 8 == 0 and n_out <= 128) else 0
+        y1, cache.q_xcache, cache.activation_outliers = mixlib.mixlinear_forward(
+            inputs, self.ind, self.q_weight, self.scale_col, self.weight_cache if n_out else None, cache.x_scale, cache.q_layout)
+        if self.bias is not None:
+            y1 += self.bias
+        return y1.reshape(cache.shape)
+
+    def _adopt_weight_columns(self, ind):
+        """``weight_cache`` grows by the dequantised weights of the new outlier columns ``ind`` (linear.py:207-212)."""
+        if self.bit == 8:
+            weight_cache = dequant_weight_columns(self.q_weight, self.scale_col, ind)
+        else:  # :210-212 (fp16 x fp16 product, like the reference's tensor expression)
+            weight_cache = mixlib.unpack_int4_to_fp16(self.q_weight, ind) * self.scale_col.T
+        self.weight_cache = weight_cache if self.ind.shape[0] == 0 else torch.hstack((self.weight_cache, weight_cache))
 
     # ---- bf16 (MI355X extension) -------------------------------------------------------------------------------------------
     def _check_bf16(self, x, cache, what):
@@ -368,13 +365,7 @@ class MixLinear_GEMM:
         assert n_out % 8 == 0 and n_out <= BF16_MAX_OUTLIERS, "a bf16 layer holds a multiple of 8 and at most 128 outlier columns (-1 padded)"
         assert cache.x_scale.numel() >= M
         if unfused and not self.add_outliers and inputs.is_contiguous():   # static set: one library call, two launches
-            cache.ind = self.ind
-            cache.q_layout = mixlib.qa_layout(M, self.out_features, self.in_features)
-            y1, cache.q_xcache, cache.activation_outliers = mixlib.mixlinear_forward(
-                inputs, self.ind, self.q_weight, self.scale_col, self.weight_cache if n_out else None, cache.x_scale, cache.q_layout)
-            if self.bias is not None:
-                y1 += self.bias
-            return y1.reshape(cache.shape)
+            return self._forward_static(inputs, cache, M)
         if unfused:   # the zeroing quantiser with the held (padded) set
             cache.q_xcache, cache.activation_outliers = mixlib.FindRowScaleFusedExtracOutliers(
                 inputs, cache.x_scale, self.ind, n_out, M, self.in_features, 0)
@@ -464,15 +455,7 @@ class MixLinear_GEMM:
         M = inputs.shape[0]
         if self.forward_without_precondition_len != cache.ind.shape[0]:
             if cache.ind.shape[0]:
-                ind = cache.new_ind
-                if self.bit == 8:
-                    weight_cache = dequant_weight_columns(self.q_weight, self.scale_col, ind)
-                else:
-                    weight_cache = mixlib.unpack_int4_to_fp16(self.q_weight, ind) * self.scale_col.T
-                if self.ind.shape[0] == 0:
-                    self.weight_cache = weight_cache
-                else:
-                    self.weight_cache = torch.hstack((self.weight_cache, weight_cache))
+                self._adopt_weight_columns(cache.new_ind)
             self.ind = cache.ind
             self.forward_without_precondition_len = self.ind.shape[0]
         y = outlier_product(cache.activation_outliers, self.weight_cache) if self.ind.shape[0] else None
@@ -525,35 +508,31 @@ class FasterTransformerRMSNorm:
         """The norm of ``x`` -- or, with ``residual``, of h = x + residual, written into ``residual`` in the same pass -- into
         ``output``, quantised for ``next_layer`` (its bit width, outlier set and preferred int8 image) when there is one."""
         add = residual is not None
-        if self.next_layer is None:
+        nxt, cache, gamma, eps = self.next_layer, self.cache, self.weight, self.variance_epsilon
+        if nxt is None:
             if add:
-                mixlib.add_layernorm_forward_cuda(x, residual, self.weight, output, self.variance_epsilon)
+                mixlib.add_layernorm_forward_cuda(x, residual, gamma, output, eps)
             else:
-                mixlib.layernorm_forward_cuda(x, self.weight, output, self.variance_epsilon)
-        elif self.next_layer.bit == 8:
+                mixlib.layernorm_forward_cuda(x, gamma, output, eps)
+        elif nxt.bit == 8:
             # decode batches: the int8 rows in the image the next layer's GEMM reads fastest (mixlib.qa_layout; the gate
             # projection that re-uses the cache has the same N).  A dynamic outlier set re-quantises row-major later.
             c = x.shape[-1]
-            m = x.numel() // c
-            n_out = int(self.next_layer.ind.shape[0])
-            lay = mixlib.qa_layout(m, self.next_layer.out_features, c) if (n_out % 8 == 0 and n_out <= 128 and
-                                                                            not self.next_layer.add_outliers) else 0
-            self.cache.q_layout = lay
+            n_out = int(nxt.ind.shape[0])
+            cache.q_layout = mixlib.qa_layout(x.numel() // c, nxt.out_features, c) if (n_out % 8 == 0 and n_out <= 128 and not nxt.add_outliers) else 0
             if add:
-                self.cache.activation_outliers, self.cache.q_xcache = mixlib.add_layernorm_forward_cuda_extract_outliers(
-                    x, residual, self.weight, output, self.variance_epsilon, self.next_layer.ind, self.cache.x_scale, lay)
+                produced = mixlib.add_layernorm_forward_cuda_extract_outliers(x, residual, gamma, output, eps, nxt.ind, cache.x_scale, cache.q_layout)
             else:
-                self.cache.activation_outliers, self.cache.q_xcache = mixlib.layernorm_forward_cuda_extract_outliers(
-                    x, self.weight, output, self.variance_epsilon, self.next_layer.ind, self.cache.x_scale, lay)
-        elif self.next_layer.bit == 4:
+                produced = mixlib.layernorm_forward_cuda_extract_outliers(x, gamma, output, eps, nxt.ind, cache.x_scale, cache.q_layout)
+            cache.activation_outliers, cache.q_xcache = produced
+        elif nxt.bit == 4:
             if self.dtype == torch.bfloat16:
                 raise TypeError("FasterTransformerRMSNorm: there is no bf16 form of the 4-bit producer (next_layer.bit == 4)")
             if add:
-                self.cache.activation_outliers, self.cache.q_xcache = mixlib.add_layernorm_forward_cuda_extract_outliers_int4(
-                    x, residual, self.weight, output, self.variance_epsilon, self.next_layer.ind, self.cache.x_scale)
+                produced = mixlib.add_layernorm_forward_cuda_extract_outliers_int4(x, residual, gamma, output, eps, nxt.ind, cache.x_scale)
             else:
-                self.cache.activation_outliers, self.cache.q_xcache = mixlib.layernorm_forward_cuda_extract_outliers_int4(
-                    x, self.weight, output, self.variance_epsilon, self.next_layer.ind, self.cache.x_scale)
+                produced = mixlib.layernorm_forward_cuda_extract_outliers_int4(x, gamma, output, eps, nxt.ind, cache.x_scale)
+            cache.activation_outliers, cache.q_xcache = produced
         else:
             raise NotImplementedError
         return output

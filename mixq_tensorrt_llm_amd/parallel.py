@@ -301,11 +301,9 @@ class PeerGather:
             tp.dst_flags[r] = self._flag_ptr(r, par, self.rank)
         tp.counters = self.small.data_ptr() + 4
         with torch.cuda.device(self.dev):
-            if bias_ptr is not None:
-                _lib.check(self.lib.mixq_enqueue_tp_bias(handle, in_desc, in_ptrs, ctypes.c_void_p(bias_ptr), ws_ptr,
-                                                         ctypes.byref(tp), st), "mixq_enqueue_tp_bias")
-            else:
-                _lib.check(self.lib.mixq_enqueue_tp(handle, in_desc, in_ptrs, ws_ptr, ctypes.byref(tp), st), "mixq_enqueue_tp")
+            # (both C entries are one call of enqueue_tp_impl; mixq_enqueue_tp passes it a null bias)
+            _lib.check(self.lib.mixq_enqueue_tp_bias(handle, in_desc, in_ptrs, ctypes.c_void_p(bias_ptr), ws_ptr, ctypes.byref(tp), st),
+                       "mixq_enqueue_tp" if bias_ptr is None else "mixq_enqueue_tp_bias")
             self._wait(par, int(self.lib.mixq_tp_flag_words(m)), st)
         return self._view(par, m)
 

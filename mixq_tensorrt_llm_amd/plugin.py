@@ -154,16 +154,11 @@ class MixQPlugin:
         out_ptrs = (ctypes.c_void_p * 1)(output.data_ptr())
         if bias is not None:
             bias = fp16_bias(bias, N, A.device, act)
-            with torch.cuda.device(A.device):
-                rc = self._lib.mixq_enqueue_bias(self._h, in_desc, ctypes.byref(out_desc), in_ptrs, out_ptrs,
-                                                 ctypes.c_void_p(bias.data_ptr()), ctypes.c_void_p(workspace.data_ptr()),
-                                                 _stream_ptr(A.device))
-            _lib.check(rc, "MixQPlugin::enqueue (bias)")
-            return output
         with torch.cuda.device(A.device):  # the library keys its per-device state on the CURRENT device
-            rc = self._lib.mixq_enqueue(self._h, in_desc, ctypes.byref(out_desc), in_ptrs, out_ptrs,
-                                        ctypes.c_void_p(workspace.data_ptr()), _stream_ptr(A.device))
-        _lib.check(rc, "MixQPlugin::enqueue")
+            rc = self._lib.mixq_enqueue_bias(self._h, in_desc, ctypes.byref(out_desc), in_ptrs, out_ptrs,   # (a null bias: mixq_enqueue)
+                                             ctypes.c_void_p(bias.data_ptr()) if bias is not None else None,
+                                             ctypes.c_void_p(workspace.data_ptr()), _stream_ptr(A.device))
+        _lib.check(rc, "MixQPlugin::enqueue" if bias is None else "MixQPlugin::enqueue (bias)")
         return output
 
 

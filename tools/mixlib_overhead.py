@@ -77,6 +77,18 @@ def main():
         if hasattr(mixlib, "mixlinear_forward"):
             res["one-call entry through mixlib.mixlinear_forward"] = bench(
                 lambda: mixlib.mixlinear_forward(x, ind, qw, sc, wc, xs))
+    # the producer-fed pair (fused norm -> gemm_mixed) at the same tiny shape, and what one more Python frame costs
+    gamma = torch.ones(K, dtype=torch.float16, device=dev)
+    normed = torch.empty_like(x)
+    res["wrapper layernorm_forward_cuda_extract_outliers"] = bench(
+        lambda: mixlib.layernorm_forward_cuda_extract_outliers(x, gamma, normed, 1e-5, ind, xs))
+    n_outl, n_q = mixlib.layernorm_forward_cuda_extract_outliers(x, gamma, normed, 1e-5, ind, xs)
+    sw = sc.reshape(N)
+    res["wrapper gemm_mixed"] = bench(lambda: mixlib.gemm_mixed(n_q, qw, xs, sw, n_outl, wc, M, N, K))
+
+    def empty():
+        pass
+    res["empty Python function call"] = bench(lambda: empty()) - bench(lambda: None)
     for k, v in res.items():
         print(f"{k:62s} {v:7.2f} us / call (host)")
     per_call = (res["wrapper: the 4-call sequence"] - res["direct ctypes: the 4-call sequence"]) / 4
