@@ -28,5 +28,6 @@ def preprocess_weights(origin_weight, is_int4=False):
 
 
 def w8_a16_gemm(input, weight, scale):
-    """w8_a16_gemm_forward_cuda (fpA_intB_gemm_wrapper.cu:29-70): fp16 [m, k] x interleaved int8 [k, n] -> fp16 [m, n]."""
+    """w8_a16_gemm_forward_cuda (fpA_intB_gemm_wrapper.cu:29-70): fp16 [m, k] x interleaved int8 [k, n] -> fp16 [m, n].
+    A bf16 ``input`` (MI355X extension; ``scale`` stays fp16) passes through unchanged and returns bf16 (``mixlib.w8_a16_gemm``)."""
     return _mixlib.w8_a16_gemm(input, weight, scale)

@@ -453,6 +453,25 @@ MIXQ_API size_t mixq_w8a16_gemm_workspace_size(int m, int n, int k);
 MIXQ_API int mixq_w8a16_gemm_forward_ws(const void* input_f16, const uint8_t* weight, const void* scale_f16,
                                         void* output_f16, int m, int n, int k, void* workspace, size_t workspace_bytes,
                                         void* stream);
+/* The same operator on fp16 or bf16 rows (MI355X extension).  `type` is MIXQ_TYPE_HALF or MIXQ_TYPE_BF16, anything else MIXQ_E_TYPE
+ * before every other check (the size query returns 0).  MIXQ_TYPE_HALF is mixq_w8a16_gemm_forward_ws, bit for bit and code for code.
+ * MIXQ_TYPE_BF16: input bf16 [m,k], output bf16 [m,n]; weight is the SAME interleaved uint8 image and scale stays fp16 [n], so one
+ * packed weight serves both types.  One rule for every m and every form:
+ *     S[m,n]   = sum_k fp32(A[m,k]) * fp32(q[k,n] - 128)      (q - 128 is exact in bf16: every product is exact in fp32; the sum is
+ *                                                              taken in fp32, in the kernel's own order)
+ *     Out[m,n] = bf16_rn( fp32(scale[n]) * S[m,n] )           (one fp32 multiply, one rounding)
+ * The weight fragments enter the bf16 MFMA unscaled; partial sums parked by a K split are unscaled fp32 and are added in rank order
+ * before the scale, so a given (shape, scratch-or-not) is deterministic and every form gives the same bits wherever the fp32 sums are
+ * exact.  No bias, no activation.  A bf16 call takes the form the fp16 call of the same (m, n, k, scratch) takes, with one exception:
+ * there is no bf16 two-pass form -- where fp16 would dequantise W into the scratch, bf16 runs the wide fused form, and
+ * mixq_w8a16_gemm_workspace_size_typed(.., MIXQ_TYPE_BF16) never includes the n k 2-byte weight image.  m <= 4 runs the bf16 GEMV /
+ * skinny kernels of a bf16 mixq_enqueue.  Checks, in this order: type; m < 0 || n < 0 || k <= 0 (BADARG); m == 0 || n == 0 (OK); null
+ * pointers (BADARG); k % 64 || n % 2 (SHAPE); input / weight 16-byte alignment (ALIGN); output alignment as above (ALIGN) except on the
+ * GEMV route; a workspace that is not 16-byte aligned is ignored.  mixq_debug_last_gemm_kernel reports the fp16 name of the form with
+ * " [bf16]" appended. */
+MIXQ_API size_t mixq_w8a16_gemm_workspace_size_typed(int m, int n, int k, int type);
+MIXQ_API int mixq_w8a16_gemm_forward_typed(const void* input, const uint8_t* weight, const void* scale_f16, void* output, int m, int n,
+                                           int k, int type, void* workspace, size_t workspace_bytes, void* stream);
 
 /* MLP fusion beyond the reference (MixQ/src/mixquant/modules/fused/mlp.py:57-64 runs int8FusedDequantizeSilu and then
  * `gate_output *= up_output` as a separate pass over [M,N]): D = fp16( fp16(silu(float(A.B^T)*(sc*sr) + y)) * mul ),
@@ -676,7 +695,8 @@ MIXQ_API const char* mixq_version(void);
  * reference-named entries (initOpenAiTritonPlugins, the plugin lifecycle, mixq_enqueue) have not changed since revision 1.
  * Revision 5 adds entries only (mixq_enqueue_bias, mixq_enqueue_tp_bias, mixq_gemm_mixed_bias; later, still 5: mixq_add_rmsnorm*,
  * mixq_rmsnorm_typed, mixq_rmsnorm_extract_quant_typed, mixq_gemm_mixed_typed, mixq_gemm_mixed_act_typed, mixq_quant_extract_typed,
- * mixq_find_outliers_typed, mixq_dequant_weight_columns_typed, mixq_mixlinear_forward_typed). */
+ * mixq_find_outliers_typed, mixq_dequant_weight_columns_typed, mixq_mixlinear_forward_typed, mixq_w8a16_gemm_workspace_size_typed,
+ * mixq_w8a16_gemm_forward_typed). */
 #define MIXQ_ABI_VERSION 5
 MIXQ_API int mixq_abi_version(void);
 MIXQ_API const char* mixq_error_string(int code);

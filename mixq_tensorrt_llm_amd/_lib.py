@@ -151,6 +151,8 @@ SIGNATURES = {
     "mixq_w8a16_gemm_forward": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "mixq_w8a16_gemm_workspace_size": (ctypes.c_size_t, [_i, _i, _i]),
     "mixq_w8a16_gemm_forward_ws": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, ctypes.c_size_t, _vp]),
+    "mixq_w8a16_gemm_workspace_size_typed": (ctypes.c_size_t, [_i, _i, _i, _i]),
+    "mixq_w8a16_gemm_forward_typed": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, ctypes.c_size_t, _vp]),
     "mixq_tp_buffer_alloc": (_i, [_sz, _i, ctypes.POINTER(_vp), _vp]),
     "mixq_tp_buffer_open": (_i, [_vp, ctypes.POINTER(_vp)]),
     "mixq_tp_buffer_close": (_i, [_vp]),

@@ -1123,29 +1123,64 @@ int mixq_dequantization_silu(void* out, const int32_t* x, const void* scaleRow, 
                                                    static_cast<hipStream_t>(stream)));
 }
 
-size_t mixq_w8a16_gemm_workspace_size(int m, int n, int k)
+// ---- fpA_intB (weight-only) GEMM: Out = A . dequant(qweight), one core for the named fp16 entries and the typed entry ----
+struct W8a16Call {
+    const void *input, *scale; // input fp16 / bf16 [m,k]; scale fp16 [n] in both types
+    const uint8_t* weight;     // the interleaved image, as stored
+    void *output, *workspace, *stream;
+    size_t workspace_bytes;
+    int m, n, k;
+    bool bf16;                 // input and output are bf16
+};
+
+static int w8a16_entry(const W8a16Call& c)
 {
-    if (m <= kSmallMFastPath || n <= 0 || k <= 0) return 0;
-    return mixq::w8a16_gemm_workspace_size(m, n, k);
+    if (c.m < 0 || c.n < 0 || c.k <= 0) return MIXQ_E_BADARG;
+    if (c.m == 0 || c.n == 0) return MIXQ_OK;
+    if (!c.input || !c.weight || !c.scale || !c.output) return MIXQ_E_BADARG;
+    if (c.k % 64 || c.n % 2) return MIXQ_E_SHAPE; // the interleaved layout needs 64-row tiles and column pairs
+    if (!aligned16(c.input) || !aligned16(c.weight)) return MIXQ_E_ALIGN;
+    hipStream_t st = static_cast<hipStream_t>(c.stream);
+    // fpA_intB_gemm_wrapper.cu:45-70: m <= SMALL_M_FAST_PATH -> the batched GEMV, else the mixed-input tensor-core GEMM
+    if (c.m <= kSmallMFastPath && !mixq::w8a16_skinny_takes(c.m, c.n, c.k)) {
+        if (!c.bf16) return hip_rc(mixq::launch_w8a16(c.input, c.weight, c.scale, c.output, c.m, c.n, c.k, st));
+        const hipError_t e = mixq::launch_w8a16_bf16(c.input, c.weight, c.scale, c.output, c.m, c.n, c.k, st, nullptr);
+        mixq::note_gemm_kernel("w8a16 GEMV (1..4 tokens) [bf16]"); // (this entry's reporting: the fp16 name of the form + " [bf16]")
+        return hip_rc(e);
+    }
+    if (c.k % 8 || !w8a16_out_aligned(c.output, c.n)) return MIXQ_E_ALIGN;
+    const void* zeros = mixq::zero_page();
+    if (!zeros) return MIXQ_E_HIP;
+    void* ws = c.workspace;
+    size_t ws_bytes = c.workspace_bytes;
+    if (ws && !aligned16(ws)) ws = nullptr, ws_bytes = 0;
+    if (c.bf16) // (1..4 tokens where the skinny form takes the shape: the kernels of launch_w8a16_skinny_bf16, the decode route of mixq_enqueue)
+        return hip_rc(mixq::launch_w8a16_gemm_bf16(c.input, c.weight, c.scale, c.output, c.m, c.n, c.k, ws, ws_bytes, zeros, st));
+    return hip_rc(mixq::launch_w8a16_gemm(c.input, c.weight, c.scale, c.output, c.m, c.n, c.k, ws, ws_bytes, zeros, st));
 }
+
+size_t mixq_w8a16_gemm_workspace_size_typed(int m, int n, int k, int type)
+{
+    if (!type_ok(type) || m <= kSmallMFastPath || n <= 0 || k <= 0) return 0;
+    return mixq::w8a16_gemm_workspace_size(m, n, k, type == MIXQ_TYPE_BF16);
+}
+
+int mixq_w8a16_gemm_forward_typed(const void* input, const uint8_t* weight, const void* scale, void* output, int m, int n, int k, int type,
+                                  void* workspace, size_t workspace_bytes, void* stream)
+{
+    if (!type_ok(type)) return MIXQ_E_TYPE;
+    W8a16Call c{};
+    c.input = input, c.weight = weight, c.scale = scale, c.output = output, c.m = m, c.n = n, c.k = k;
+    c.workspace = workspace, c.workspace_bytes = workspace_bytes, c.stream = stream, c.bf16 = type == MIXQ_TYPE_BF16;
+    return w8a16_entry(c);
+}
+// the named fp16 forms: the typed entry with fewer operands
+size_t mixq_w8a16_gemm_workspace_size(int m, int n, int k) { return mixq_w8a16_gemm_workspace_size_typed(m, n, k, MIXQ_TYPE_HALF); }
 
 int mixq_w8a16_gemm_forward_ws(const void* input, const uint8_t* weight, const void* scale, void* output, int m, int n,
                                int k, void* workspace, size_t workspace_bytes, void* stream)
 {
-    if (m < 0 || n < 0 || k <= 0) return MIXQ_E_BADARG;
-    if (m == 0 || n == 0) return MIXQ_OK;
-    if (!input || !weight || !scale || !output) return MIXQ_E_BADARG;
-    if (k % 64 || n % 2) return MIXQ_E_SHAPE; // the interleaved layout needs 64-row tiles and column pairs
-    if (!aligned16(input) || !aligned16(weight)) return MIXQ_E_ALIGN;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    // fpA_intB_gemm_wrapper.cu:45-70: m <= SMALL_M_FAST_PATH -> the batched GEMV, else the mixed-input tensor-core GEMM
-    if (m <= kSmallMFastPath && !mixq::w8a16_skinny_takes(m, n, k))
-        return hip_rc(mixq::launch_w8a16(input, weight, scale, output, m, n, k, st));
-    if (k % 8 || !w8a16_out_aligned(output, n)) return MIXQ_E_ALIGN;
-    const void* zeros = mixq::zero_page();
-    if (!zeros) return MIXQ_E_HIP;
-    if (workspace && !aligned16(workspace)) workspace = nullptr, workspace_bytes = 0;
-    return hip_rc(mixq::launch_w8a16_gemm(input, weight, scale, output, m, n, k, workspace, workspace_bytes, zeros, st));
+    return mixq_w8a16_gemm_forward_typed(input, weight, scale, output, m, n, k, MIXQ_TYPE_HALF, workspace, workspace_bytes, stream);
 }
 
 int mixq_w8a16_gemm_forward(const void* input, const uint8_t* weight, const void* scale, void* output, int m, int n,

@@ -279,8 +279,12 @@ hipError_t launch_tp_wait(const unsigned* flags, int nprod, int word0, int nword
 hipError_t launch_tp_arrive(unsigned* const* peer_acks, const unsigned* own_acks, int npeer, const unsigned* seq_word,
                             unsigned* status, int trap, unsigned patience_ms, hipStream_t st);
 // fpA_intB GEMM (M > 4) on the interleaved qweight (w8a16_gemm_kernels.hip); scratch may be null (no K split)
-size_t w8a16_gemm_workspace_size(int M, int N, int K);
+size_t w8a16_gemm_workspace_size(int M, int N, int K, bool bf16 = false);
 hipError_t launch_w8a16_gemm(const void* A, const uint8_t* Wq, const void* scale, void* Out, int M, int N, int K,
                              void* scratch, size_t scratch_bytes, const void* zeros, hipStream_t st);
+// the bf16 call: A / Out bf16, scale fp16; Out = bf16(scale[n] * sum_k A[m,k] (q[k,n] - 128)), the form of the fp16 call of the same
+// shape and scratch (the wide form where that is the two-pass form)
+hipError_t launch_w8a16_gemm_bf16(const void* A, const uint8_t* Wq, const void* scale, void* Out, int M, int N, int K,
+                                  void* scratch, size_t scratch_bytes, const void* zeros, hipStream_t st);
 
 } // namespace mixq

@@ -27,6 +27,11 @@
 // scratch): every workgroup parks its fp32 partial tile with write-through stores and counts itself in; the LAST one to
 // arrive adds all parts IN RANK ORDER (fp32 addition does not commute bitwise: a fixed order keeps the result
 // deterministic whichever workgroup is last) and stores the fp16 tile.  Nobody waits.
+//
+// bf16 calls (template parameter BF of the narrow and the wide kernel, w8a16_skinny_bf16_kernel; MI355X extension, no reference
+// counterpart): Out[m,n] = bf16(scale[n] * sum_k A[m,k] (q[k,n] - 128)) -- bf16 activations, the SAME weight image and fp16 scales.
+// q - 128 is exact in bf16, so the fragments enter the bf16 MFMA unscaled and every product is exact in fp32; the column scale leaves
+// the main loop and multiplies the reduced fp32 sum once, in the store path, before the single bf16 rounding.
 #include <type_traits>
 
 #include "mixq_device.h"
@@ -47,9 +52,43 @@ __device__ __forceinline__ v2h wo_dequant_pair(unsigned w, unsigned sel, v2h sca
     return (__builtin_bit_cast(v2h, h) + bias) * scale2; // exact subtract, one RNE in the multiply
 }
 
+// bf16 calls (BF): one interleaved word -> the bf16 pairs (byte - 128) of its even bytes (0, 2) and of its odd bytes (1, 3).  Exact:
+// v_perm_b32 builds the fp32 0x4B0000bb = 2^23 + byte, the packed fp32 add takes 2^23 + 128 off, and |byte - 128| <= 128 has 8
+// significant bits, so the upper half of the difference IS the bf16 value (a second v_perm_b32 packs two of them).  Per pair: two
+// v_perm_b32, one v_pk_add_f32 (two per word), one v_perm_b32 = 4 VALU against the fp16 sequence's 3, and no scale multiply: the column
+// scale multiplies the fp32 sum once, in the epilogue.  (wpair_bf16 -- shift, convert, subtract per byte -- is 5.)
+__device__ __forceinline__ void wo_bf16_pairs(unsigned w, unsigned& even, unsigned& odd)
+{
+    typedef float v2f_ __attribute__((ext_vector_type(2)));
+    const unsigned magic = 0x4B000000u; // selectors: byte 3 = the 0x4B, bytes 2, 1 = 0x00, byte 0 = byte b of w
+    const float f0 = __builtin_bit_cast(float, __builtin_amdgcn_perm(magic, w, 0x070c0c00u));
+    const float f1 = __builtin_bit_cast(float, __builtin_amdgcn_perm(magic, w, 0x070c0c01u));
+    const float f2 = __builtin_bit_cast(float, __builtin_amdgcn_perm(magic, w, 0x070c0c02u));
+    const float f3 = __builtin_bit_cast(float, __builtin_amdgcn_perm(magic, w, 0x070c0c03u));
+    const v2f_ off = {8388736.f, 8388736.f}; // 2^23 + 128
+    const v2f_ fe = v2f_{f0, f2} - off, fo = v2f_{f1, f3} - off;
+    // (scalars first: __builtin_bit_cast of a vector ELEMENT reads element 0 whatever the index -- seen in the ISA of this helper)
+    const float e0 = fe[0], e1 = fe[1], o0 = fo[0], o1 = fo[1];
+    even = __builtin_amdgcn_perm(__builtin_bit_cast(unsigned, e1), __builtin_bit_cast(unsigned, e0), 0x07060302u);
+    odd = __builtin_amdgcn_perm(__builtin_bit_cast(unsigned, o1), __builtin_bit_cast(unsigned, o0), 0x07060302u);
+}
+// bf16 calls: the fp16 column scales of output columns n .. n + 3 (clamped: columns past N are computed, never stored) times four
+// reduced fp32 sums, each rounded once to bf16 -- Out = bf16_rn(fp32(scale[n]) * S[m,n])
+__device__ __forceinline__ void wo_scale_round_bf16(const uint16_t* __restrict__ scale, int n, int N, float s0, float s1, float s2,
+                                                    float s3, v2h& lo, v2h& hi)
+{
+    float sc[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) sc[r] = h2f(scale[min(n + r, N - 1)]);
+    lo = f2bf2_of_f32_results(s0 * sc[0], s1 * sc[1]);
+    hi = f2bf2_of_f32_results(s2 * sc[2], s3 * sc[3]);
+}
+
 // WM = 1: 4 waves, each 32 columns x all 32*MT rows.  WM = 2: 8 waves, the second four take the upper half of the rows
 // (two waves per SIMD: one wave's LDS reads and dequant VALU hide under the other's MFMAs -- the large-M form).
-template <int MT, int NST, int WM = 1>
+// BF: the bf16 call -- A and Out are bf16, the weight fragments are the exact bf16 (q - 128), UNSCALED, on v_mfma_f32_32x32x16_bf16;
+// parked K-split partials are unscaled fp32 sums; the fp16 column scale multiplies the reduced sum once before the one bf16 rounding.
+template <int MT, int NST, int WM = 1, bool BF = false>
 __global__ __launch_bounds__(256 * WM) void w8a16_gemm_kernel(const uint16_t* __restrict__ A, const uint8_t* __restrict__ Wq,
                                                           const uint16_t* __restrict__ scale,
                                                           uint16_t* __restrict__ Out, int M, int N, int K, int ks,
@@ -83,8 +122,8 @@ __global__ __launch_bounds__(256 * WM) void w8a16_gemm_kernel(const uint16_t* __
     // asm-form loads (wave-uniform base of the stage + this lane's offset), NOT counted by the compiler: see gload16_sbase
     const int ncol = min(n0w + lr, N - 1);        // clamped columns are computed, never stored
     const unsigned wlane = (unsigned)(ncol >> 1) * 2u * (unsigned)K + (unsigned)((ncol & 1) * 64 + lh * 16); // N K < 2^32
-    v2h scale2;
-    {
+    v2h scale2 = {(_Float16)0.f, (_Float16)0.f};
+    if constexpr (!BF) {
         _Float16 sc;
         const uint16_t sb = scale[ncol];
         __builtin_memcpy(&sc, &sb, 2);
@@ -146,6 +185,21 @@ __global__ __launch_bounds__(256 * WM) void w8a16_gemm_kernel(const uint16_t* __
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             const unsigned d[4] = {w[q][0], w[q][1], w[q][2], w[q][3]};
+            if constexpr (BF) {
+                unsigned e[4], o[4];
+#pragma unroll
+                for (int x = 0; x < 4; ++x) wo_bf16_pairs(d[x], e[x], o[x]); // bytes 0, 2 | bytes 1, 3, as below
+                const v4u ew = {e[0], e[1], e[2], e[3]}, ow = {o[0], o[1], o[2], o[3]};
+                const v8h we = __builtin_bit_cast(v8h, ew), wod = __builtin_bit_cast(v8h, ow);
+#pragma unroll
+                for (int t = 0; t < MTW; ++t) {
+                    const v8h ae = *reinterpret_cast<const v8h*>(base + t * 32 * ROWB + aoff[q][0]);
+                    const v8h ao = *reinterpret_cast<const v8h*>(base + t * 32 * ROWB + aoff[q][1]);
+                    acc[t] = mfma32_o<true>(we, ae, acc[t]);
+                    acc[t] = mfma32_o<true>(wod, ao, acc[t]);
+                }
+                continue;
+            }
             v2h e2[4], o2[4];
 #pragma unroll
             for (int x = 0; x < 4; ++x) {
@@ -247,7 +301,12 @@ __global__ __launch_bounds__(256 * WM) void w8a16_gemm_kernel(const uint16_t* __
         for (int g = 0; g < 4; ++g) {
             const int n = n0w + 8 * g + 4 * lh;
             uint16_t* dst = Out + (int64_t)m * N + n;
-            const v2h lo = f2h2(acc[t][4 * g], acc[t][4 * g + 1]), hi = f2h2(acc[t][4 * g + 2], acc[t][4 * g + 3]);
+            v2h lo, hi;
+            if constexpr (BF) {
+                wo_scale_round_bf16(scale, n, N, acc[t][4 * g], acc[t][4 * g + 1], acc[t][4 * g + 2], acc[t][4 * g + 3], lo, hi);
+            } else {
+                lo = f2h2(acc[t][4 * g], acc[t][4 * g + 1]), hi = f2h2(acc[t][4 * g + 2], acc[t][4 * g + 3]);
+            }
             if (n + 3 < N && (N & 3) == 0) { // (rows of N % 4 == 2 columns start 4 bytes off every other row: dword stores)
                 *reinterpret_cast<uint2*>(dst) = uint2{__builtin_bit_cast(unsigned, lo), __builtin_bit_cast(unsigned, hi)};
             } else {
@@ -295,7 +354,9 @@ constexpr int WSTAGE = BNW * KBW; // weight bytes per stage
 // skip LDS -- each lane loads its own 16-byte groups straight into registers (asm form, gload16_sbase), NST - 1 stages
 // ahead like the token copies.  A register load costs the issuing wave a few cycles where an LDS-DMA copy costs 60-185,
 // and the ds_read_b128 of the weight groups disappear; LDS holds token stages only.
-template <int MTW, int WMH, int NST, int ABL = 0, bool RW = false>
+// BF: the bf16 call, as in w8a16_gemm_kernel -- exact unscaled bf16 weight fragments on the bf16 MFMA; the partial tiles of the two K
+// halves and of a K split over workgroups are unscaled fp32; scale and the one bf16 rounding in the store path.
+template <int MTW, int WMH, int NST, int ABL = 0, bool RW = false, bool BF = false>
 __global__ __launch_bounds__(256 * (WMH == 3 ? 2 : WMH)) void w8a16_gemm_wide_kernel(const uint16_t* __restrict__ A, const uint8_t* __restrict__ Wq,
                                                                const uint16_t* __restrict__ scale,
                                                                uint16_t* __restrict__ Out, int M, int N, int K, int ks,
@@ -308,6 +369,7 @@ __global__ __launch_bounds__(256 * (WMH == 3 ? 2 : WMH)) void w8a16_gemm_wide_ke
     constexpr int TA = KH ? 256 : T;              // threads that hold finished accumulators (K halves: waves 0-3 after the merge)
     static_assert(!RW || WMH != 2, "register weights: one wave per column group and k step");
     static_assert(!RW || ABL == 0, "");
+    static_assert(!BF || ABL == 0, "the ablations are fp16 measurements");
     constexpr int ASTAGE = ROWS * ROWBW;          // token bytes of one stage
     constexpr int STAGE = ASTAGE + (RW ? 0 : WSTAGE); // [tokens | raw weights]
     constexpr int AL = ROWS * 8 / T;              // token copies (16 B) per thread per stage
@@ -420,7 +482,7 @@ __global__ __launch_bounds__(256 * (WMH == 3 ? 2 : WMH)) void w8a16_gemm_wide_ke
 #pragma unroll
         for (int cb = 0; cb < 2; ++cb) woff[cb][0] = woff[cb][1];
     }
-    v2h scale2[2];
+    v2h scale2[2]; // (BF: never used -- the scale waits for the store path -- and these loads drop out of the build)
 #pragma unroll
     for (int cb = 0; cb < 2; ++cb) {
         _Float16 sc;
@@ -448,6 +510,14 @@ __global__ __launch_bounds__(256 * (WMH == 3 ? 2 : WMH)) void w8a16_gemm_wide_ke
     v2h E[2][2][4], O[2][2][4]; // [k step j][column block][x]: dequantised operands (even / odd k halves of a 16-byte group)
     auto dequant_half = [&](const uint4& wv, int h, v2h sc, v2h (&e2)[4], v2h (&o2)[4]) __attribute__((always_inline)) {
         const unsigned d0 = h ? wv.z : wv.x, d1 = h ? wv.w : wv.y;
+        if constexpr (BF) { // (the operands travel as the bits of v2h: E / O, the fragment builds and the LDS reads stay one text)
+            unsigned e, o;
+            wo_bf16_pairs(d0, e, o);
+            e2[2 * h] = __builtin_bit_cast(v2h, e), o2[2 * h] = __builtin_bit_cast(v2h, o);
+            wo_bf16_pairs(d1, e, o);
+            e2[2 * h + 1] = __builtin_bit_cast(v2h, e), o2[2 * h + 1] = __builtin_bit_cast(v2h, o);
+            return;
+        }
         if (ABL & 2) {
             e2[2 * h] = o2[2 * h] = __builtin_bit_cast(v2h, d0);
             e2[2 * h + 1] = o2[2 * h + 1] = __builtin_bit_cast(v2h, d1);
@@ -497,6 +567,11 @@ __global__ __launch_bounds__(256 * (WMH == 3 ? 2 : WMH)) void w8a16_gemm_wide_ke
             if (ABL & 8) {
                 acc[0][t][0] += we0[0] * fa[fc][0] + wo0[1] * fo[fc][1];
                 acc[1][t][0] += we1[0] * fa[fc][0] + wo1[1] * fo[fc][1];
+            } else if constexpr (BF) {
+                acc[0][t] = mfma32_o<true>(we0, fa[fc], acc[0][t]);
+                acc[1][t] = mfma32_o<true>(we1, fa[fc], acc[1][t]);
+                acc[0][t] = mfma32_o<true>(wo0, fo[fc], acc[0][t]);
+                acc[1][t] = mfma32_o<true>(wo1, fo[fc], acc[1][t]);
             } else {
                 acc[0][t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(we0, fa[fc], acc[0][t], 0, 0, 0);
                 acc[1][t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(we1, fa[fc], acc[1][t], 0, 0, 0);
@@ -522,7 +597,8 @@ __global__ __launch_bounds__(256 * (WMH == 3 ? 2 : WMH)) void w8a16_gemm_wide_ke
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
                     __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                    if (DEQ && takes) __builtin_amdgcn_sched_group_barrier(0x002, 3 * UNITS_LO, 0);
+                    // (VALU per (cb, h) unit and MFMA: fp16 perm / pk_add / pk_mul per pair = 3; bf16 2 perm / pk_add_f32 / perm per pair = 4)
+                    if (DEQ && takes) __builtin_amdgcn_sched_group_barrier(0x002, (BF ? 4 : 3) * UNITS_LO, 0);
                 }
             }
         }
@@ -635,7 +711,11 @@ __global__ __launch_bounds__(256 * (WMH == 3 ? 2 : WMH)) void w8a16_gemm_wide_ke
         constexpr int NE = 2 * MTW * 16; // floats per lane
         if (!holder) {
             // (K halves: waves 4-7 have nothing left to do)
-        } else if constexpr (NE <= 64) {
+        } else if constexpr (NE <= 64 && !(BF && NE == 64 && T == 512)) {
+            // (BF, 8 waves x 64 rows -- configurations 3 and 5: 256 registers per lane; cur + nxt + sum and their addresses spill 4 of
+            //  them, in the fp16 builds too.  The bf16 builds give up the next rank's prefetch instead -- the loop below, the same
+            //  rank order and the same bits -- so that no bf16 build touches scratch memory; the depth of the main loop's prefetch
+            //  has no part in it.)
             // short tiles (32 / 64 rows, split up to 16 ways): the NEXT rank's loads are in flight while this rank's are
             // added -- a rank at a time costs one memory round trip per rank (~1.3 us x ks on a 25-us launch)
             float* const accf = reinterpret_cast<float*>(&acc[0][0]); // element q <-> parked word q * TA, q = (cb * MTW + t) * 16 + e
@@ -693,8 +773,14 @@ __global__ __launch_bounds__(256 * (WMH == 3 ? 2 : WMH)) void w8a16_gemm_wide_ke
             for (int g = 0; g < 4; ++g) {
                 const int n = n0w + cb * 32 + 8 * g + 4 * lh;
                 uint16_t* dst = Out + (int64_t)m * N + n;
-                const v2h lo = f2h2(acc[cb][t][4 * g], acc[cb][t][4 * g + 1]);
-                const v2h hi = f2h2(acc[cb][t][4 * g + 2], acc[cb][t][4 * g + 3]);
+                v2h lo, hi;
+                if constexpr (BF) {
+                    wo_scale_round_bf16(scale, n, N, acc[cb][t][4 * g], acc[cb][t][4 * g + 1], acc[cb][t][4 * g + 2],
+                                        acc[cb][t][4 * g + 3], lo, hi);
+                } else {
+                    lo = f2h2(acc[cb][t][4 * g], acc[cb][t][4 * g + 1]);
+                    hi = f2h2(acc[cb][t][4 * g + 2], acc[cb][t][4 * g + 3]);
+                }
                 if (n + 3 < N && (N & 3) == 0) { // (rows of N % 4 == 2 columns start 4 bytes off every other row: dword stores)
                     *reinterpret_cast<uint2*>(dst) = uint2{__builtin_bit_cast(unsigned, lo), __builtin_bit_cast(unsigned, hi)};
                 } else {
@@ -1184,12 +1270,14 @@ static size_t wo_two_pass_bytes(int N, int K) { return kSplitkWordsBytes + (size
 
 bool w8a16_skinny_takes(int M, int N, int K) { return wo_skinny_pick(M, N, K) != 0; }
 
-size_t w8a16_gemm_workspace_size(int M, int N, int K)
+// bf16: a bf16 call has no two-pass form (no bf16 main loop in the ping-pong kernel yet): where fp16 plans two passes it takes the wide
+// form, and its scratch never holds a weight image
+size_t w8a16_gemm_workspace_size(int M, int N, int K, bool bf16)
 {
     if (N <= 0 || K <= 0) return 0;
     if (wo_skinny_pick(M, N, K) != 0) return 0; // (K is split inside the workgroup)
     if (M <= 4) return 0;
-    if (wo_two_pass_wanted(M, N, K)) { // (a smaller scratch still serves the wide form's K split, or none)
+    if (!bf16 && wo_two_pass_wanted(M, N, K)) { // (a smaller scratch still serves the wide form's K split, or none)
         const size_t wide = wo_wide_plan(M, N, K, true).cfg != 0 ? wo_wide_workspace(M, N, K) : 0;
         return wo_two_pass_bytes(N, K) > wide ? wo_two_pass_bytes(N, K) : wide;
     }
@@ -1200,13 +1288,13 @@ size_t w8a16_gemm_workspace_size(int M, int N, int K)
     return full > tail ? full : tail;
 }
 
-template <int MT, int NST, int WM = 1>
+template <int MT, int NST, int WM = 1, bool BF = false>
 static hipError_t launch_wo(const uint16_t* A, const uint8_t* Wq, const uint16_t* scale, uint16_t* Out, int M, int N,
                             int K, int ks, void* scratch, const void* zeros, hipStream_t st)
 {
     constexpr size_t lds = (size_t)NST * MT * 32 * wo::ROWB;
     static_assert(lds <= 160 * 1024 - 64, "LDS budget");
-    auto kern = w8a16_gemm_kernel<MT, NST, WM>;
+    auto kern = w8a16_gemm_kernel<MT, NST, WM, BF>;
     static DeviceOnce once;
     if (hipError_t e = ensure_dynamic_lds(kern, lds, once); e != hipSuccess) return e;
     const int ntiles = (N + wo::BN - 1) / wo::BN;
@@ -1235,10 +1323,13 @@ static hipError_t launch_wo_skinny_bf16(const uint16_t* A, const uint8_t* Wq, co
                                         int K, hipStream_t st, const uint16_t* bias)
 {
     const dim3 grid((unsigned)((N + 16 * CG - 1) / (16 * CG))), block(KW * 64);
-    if (g_wo_nt.load() != 0 && (int64_t)N * K >= wo_nt_weight_bytes()) // (launch_wo_skinny's rule for MT == 1)
-        hipLaunchKernelGGL((w8a16_skinny_bf16_kernel<MT, KW, CG, true, BIAS>), grid, block, 0, st, A, Wq, scale, Out, M, N, K, bias);
-    else
-        hipLaunchKernelGGL((w8a16_skinny_bf16_kernel<MT, KW, CG, false, BIAS>), grid, block, 0, st, A, Wq, scale, Out, M, N, K, bias);
+    if constexpr (MT == 1) { // (launch_wo_skinny's rule: non-temporal weight loads on the one-tile forms only)
+        if (g_wo_nt.load() != 0 && (int64_t)N * K >= wo_nt_weight_bytes()) {
+            hipLaunchKernelGGL((w8a16_skinny_bf16_kernel<MT, KW, CG, true, BIAS>), grid, block, 0, st, A, Wq, scale, Out, M, N, K, bias);
+            return hipGetLastError();
+        }
+    }
+    hipLaunchKernelGGL((w8a16_skinny_bf16_kernel<MT, KW, CG, false, BIAS>), grid, block, 0, st, A, Wq, scale, Out, M, N, K, bias);
     return hipGetLastError();
 }
 template <bool BIAS>
@@ -1290,7 +1381,7 @@ hipError_t launch_w8a16_skinny_bias(const void* A, const uint8_t* Wq, const void
     }
 }
 
-template <int MTW, int WMH, int NST, int ABL = 0, bool RW = false>
+template <int MTW, int WMH, int NST, int ABL = 0, bool RW = false, bool BF = false>
 static hipError_t launch_wo_wide(const uint16_t* A, const uint8_t* Wq, const uint16_t* scale, uint16_t* Out, int M, int N,
                                  int K, int ks, void* scratch, hipStream_t st)
 {
@@ -1299,7 +1390,7 @@ static hipError_t launch_wo_wide(const uint16_t* A, const uint8_t* Wq, const uin
     constexpr size_t merge = WMH == 3 ? (size_t)2 * MTW * 16 * 256 * sizeof(float) : 0; // K halves meet in LDS after the loop
     constexpr size_t lds = stages > merge ? stages : merge;
     static_assert(lds <= 160 * 1024 - 64, "LDS budget");
-    auto kern = w8a16_gemm_wide_kernel<MTW, WMH, NST, ABL, RW>;
+    auto kern = w8a16_gemm_wide_kernel<MTW, WMH, NST, ABL, RW, BF>;
     static DeviceOnce once;
     if (hipError_t e = ensure_dynamic_lds(kern, lds, once); e != hipSuccess) return e;
     const int tiles = ((M + rows - 1) / rows) * ((N + wo::BNW - 1) / wo::BNW);
@@ -1308,27 +1399,35 @@ static hipError_t launch_wo_wide(const uint16_t* A, const uint8_t* Wq, const uin
     return hipGetLastError();
 }
 
-// Reporting only (mixq_debug_last_gemm_kernel): the form a call took -- "w8a16 wide cfg<1..6>[ registers][, K split over workgroups]"
-#define MIXQ_WO_WIDE_NAMES(c)                                                                          \
-    {{"w8a16 wide cfg" #c, "w8a16 wide cfg" #c ", K split over workgroups"},                             \
-     {"w8a16 wide cfg" #c " registers", "w8a16 wide cfg" #c " registers, K split over workgroups"}}
-static const char* wo_wide_name(int cfg, bool regs, bool split)
+// Reporting only (mixq_debug_last_gemm_kernel): the form a call took -- "w8a16 wide cfg<1..6>[ registers][, K split over workgroups]";
+// a bf16 call reports the fp16 name of its form with " [bf16]" appended
+#define MIXQ_WO_BF16_NAME(bf, name) ((bf) ? name " [bf16]" : name)
+#define MIXQ_WO_WIDE_NAMES2(c, sfx)                                                                                \
+    {{"w8a16 wide cfg" #c sfx, "w8a16 wide cfg" #c ", K split over workgroups" sfx},                                 \
+     {"w8a16 wide cfg" #c " registers" sfx, "w8a16 wide cfg" #c " registers, K split over workgroups" sfx}}
+#define MIXQ_WO_WIDE_NAMES(c) {MIXQ_WO_WIDE_NAMES2(c, ""), MIXQ_WO_WIDE_NAMES2(c, " [bf16]")}
+static const char* wo_wide_name(int cfg, bool regs, bool split, bool bf16 = false)
 {
-    static const char* const names[7][2][2] = {MIXQ_WO_WIDE_NAMES(0), MIXQ_WO_WIDE_NAMES(1), MIXQ_WO_WIDE_NAMES(2), MIXQ_WO_WIDE_NAMES(3),
-                                               MIXQ_WO_WIDE_NAMES(4), MIXQ_WO_WIDE_NAMES(5), MIXQ_WO_WIDE_NAMES(6)};
-    return names[cfg >= 0 && cfg < 7 ? cfg : 0][regs ? 1 : 0][split ? 1 : 0];
+    static const char* const names[7][2][2][2] = {MIXQ_WO_WIDE_NAMES(0), MIXQ_WO_WIDE_NAMES(1), MIXQ_WO_WIDE_NAMES(2), MIXQ_WO_WIDE_NAMES(3),
+                                                  MIXQ_WO_WIDE_NAMES(4), MIXQ_WO_WIDE_NAMES(5), MIXQ_WO_WIDE_NAMES(6)};
+    return names[cfg >= 0 && cfg < 7 ? cfg : 0][bf16 ? 1 : 0][regs ? 1 : 0][split ? 1 : 0];
 }
 #undef MIXQ_WO_WIDE_NAMES
+#undef MIXQ_WO_WIDE_NAMES2
 
-hipError_t launch_w8a16_gemm(const void* A, const uint8_t* Wq, const void* scale, void* Out, int M, int N, int K,
-                             void* scratch, size_t scratch_bytes, const void* zeros, hipStream_t st)
+// BF: the bf16 call.  It takes the form, tile, K split and scratch layout the fp16 call of the same (M, N, K, scratch) takes -- the
+// picks and plans below do not look at the type, and the measurement knobs act on both -- except where fp16 goes two-pass: there is
+// no bf16 build of that form, such a call takes the wide form.  (The cost tables were fitted on fp16 timings.)
+template <bool BF>
+static hipError_t launch_w8a16_gemm_t(const void* A, const uint8_t* Wq, const void* scale, void* Out, int M, int N, int K,
+                                      void* scratch, size_t scratch_bytes, const void* zeros, hipStream_t st)
 {
     if (M <= 0 || N <= 0) return hipSuccess;
     const uint16_t* a = static_cast<const uint16_t*>(A);
     const uint16_t* s = static_cast<const uint16_t*>(scale);
     uint16_t* o = static_cast<uint16_t*>(Out);
     // (the second pass stores whole 16-byte pieces of an output row: an output that is not 16-byte aligned keeps the fused forms)
-    if (wo_two_pass_wanted(M, N, K) && scratch != nullptr && scratch_bytes >= wo_two_pass_bytes(N, K) && (reinterpret_cast<uintptr_t>(Out) & 15u) == 0) {
+    if (!BF && wo_two_pass_wanted(M, N, K) && scratch != nullptr && scratch_bytes >= wo_two_pass_bytes(N, K) && (reinterpret_cast<uintptr_t>(Out) & 15u) == 0) {
         const int64_t groups = (int64_t)(N >> 1) * (K >> 3);
         uint16_t* const wf = reinterpret_cast<uint16_t*>(static_cast<char*>(scratch) + kSplitkWordsBytes);
         hipLaunchKernelGGL(w8a16_dequant_kernel, dim3((unsigned)((groups + 255) / 256)), dim3(256), 0, st, Wq, s, wf, N, K);
@@ -1339,7 +1438,23 @@ hipError_t launch_w8a16_gemm(const void* A, const uint8_t* Wq, const void* scale
         return launch_gemm_f16_pp(A, wf, Out, M, N, K, zeros, st);
     }
     if (const int pick = wo_skinny_pick(M, N, K); pick != 0) {
-        note_gemm_kernel("w8a16 skinny (MFMA GEMV, K split inside the workgroup)");
+        note_gemm_kernel(MIXQ_WO_BF16_NAME(BF, "w8a16 skinny (MFMA GEMV, K split inside the workgroup)"));
+        if constexpr (BF) { // the same (token tiles, waves, column groups) per pick as below
+            if (M <= 16) return launch_wo_skinny_bf16_pick<false>(pick, a, Wq, s, o, M, N, K, st, nullptr);
+            if (M <= 32) {
+                switch (pick) {
+                case 2: return launch_wo_skinny_bf16<2, 8, 2, false>(a, Wq, s, o, M, N, K, st, nullptr);
+                case 3: return launch_wo_skinny_bf16<2, 16, 2, false>(a, Wq, s, o, M, N, K, st, nullptr);
+                case 4: return launch_wo_skinny_bf16<2, 8, 4, false>(a, Wq, s, o, M, N, K, st, nullptr);
+                default: return launch_wo_skinny_bf16<2, 16, 4, false>(a, Wq, s, o, M, N, K, st, nullptr);
+                }
+            }
+            if (M <= 48)
+                return pick <= 3 ? launch_wo_skinny_bf16<3, 8, 2, false>(a, Wq, s, o, M, N, K, st, nullptr)
+                                 : launch_wo_skinny_bf16<3, 8, 4, false>(a, Wq, s, o, M, N, K, st, nullptr);
+            return pick <= 3 ? launch_wo_skinny_bf16<4, 8, 2, false>(a, Wq, s, o, M, N, K, st, nullptr)
+                             : launch_wo_skinny_bf16<4, 8, 4, false>(a, Wq, s, o, M, N, K, st, nullptr);
+        }
         if (M <= 16) {
             switch (pick) {
             case 2: return launch_wo_skinny<1, 8, 2>(a, Wq, s, o, M, N, K, st);
@@ -1361,11 +1476,31 @@ hipError_t launch_w8a16_gemm(const void* A, const uint8_t* Wq, const void* scale
         if (M <= 48) return pick <= 3 ? launch_wo_skinny<3, 8, 2>(a, Wq, s, o, M, N, K, st) : launch_wo_skinny<3, 8, 4>(a, Wq, s, o, M, N, K, st);
         return pick <= 3 ? launch_wo_skinny<4, 8, 2>(a, Wq, s, o, M, N, K, st) : launch_wo_skinny<4, 8, 4>(a, Wq, s, o, M, N, K, st);
     }
+    const int abl = BF ? 0 : g_wo_abl.load(); // (the ablation builds are fp16 measurements)
     const size_t need_wide = wo_wide_workspace(M, N, K); // 0: the plan with scratch is the narrow form or does not split K
     const WoWidePlan pl = wo_wide_plan(M, N, K, need_wide == 0 || (scratch != nullptr && scratch_bytes >= need_wide));
     if (pl.cfg != 0) {
-        note_gemm_kernel(wo_wide_name(pl.cfg, g_wo_rw.load() != 0 && g_wo_abl.load() == 0 && (pl.cfg == 1 || pl.cfg == 2 || pl.cfg == 5 || pl.cfg == 6),
-                                      pl.ks > 1));
+        note_gemm_kernel(wo_wide_name(pl.cfg, g_wo_rw.load() != 0 && abl == 0 && (pl.cfg == 1 || pl.cfg == 2 || pl.cfg == 5 || pl.cfg == 6),
+                                      pl.ks > 1, BF));
+        if constexpr (BF) {
+            if (g_wo_rw.load() != 0) {
+                switch (pl.cfg) {
+                case 1: return launch_wo_wide<1, 1, 6, 0, true, true>(a, Wq, s, o, M, N, K, pl.ks, scratch, st);
+                case 2: return launch_wo_wide<2, 1, 6, 0, true, true>(a, Wq, s, o, M, N, K, pl.ks, scratch, st);
+                case 5: return launch_wo_wide<2, 3, 6, 0, true, true>(a, Wq, s, o, M, N, K, pl.ks, scratch, st);
+                case 6: return launch_wo_wide<4, 3, 4, 0, true, true>(a, Wq, s, o, M, N, K, pl.ks, scratch, st);
+                default: break;
+                }
+            }
+            switch (pl.cfg) {
+            case 1: return launch_wo_wide<1, 1, 6, 0, false, true>(a, Wq, s, o, M, N, K, pl.ks, scratch, st);
+            case 2: return launch_wo_wide<2, 1, 6, 0, false, true>(a, Wq, s, o, M, N, K, pl.ks, scratch, st);
+            case 3: return launch_wo_wide<2, 2, 4, 0, false, true>(a, Wq, s, o, M, N, K, pl.ks, scratch, st);
+            case 5: return launch_wo_wide<2, 3, 6, 0, false, true>(a, Wq, s, o, M, N, K, pl.ks, scratch, st);
+            case 6: return launch_wo_wide<4, 3, 4, 0, false, true>(a, Wq, s, o, M, N, K, pl.ks, scratch, st);
+            default: return launch_wo_wide<4, 2, 3, 0, false, true>(a, Wq, s, o, M, N, K, pl.ks, scratch, st);
+            }
+        }
         if (pl.cfg == 4) {
             switch (g_wo_abl.load()) { // measurement-only ablations of the 256-row form
             case 1: return launch_wo_wide<4, 2, 3, 1>(a, Wq, s, o, M, N, K, pl.ks, scratch, st);
@@ -1411,7 +1546,7 @@ hipError_t launch_w8a16_gemm(const void* A, const uint8_t* Wq, const void* scale
     // the narrow form addresses the weights with an absolute 32-bit per-lane offset (w8a16_gemm_kernel: wlane): a weight of 4 GiB
     // or more (a 256k-entry head on K = 16384) would wrap silently -- refuse it (the wide / skinny forms use 64-bit bases)
     if ((int64_t)N * (int64_t)K >= ((int64_t)1 << 32)) return hipErrorInvalidValue;
-    note_gemm_kernel("w8a16 narrow (256-token passes)");
+    note_gemm_kernel(MIXQ_WO_BF16_NAME(BF, "w8a16 narrow (256-token passes)"));
     for (int m0 = 0; m0 < M; m0 += 256) { // 256-token passes (each streams the weights once)
         const int rows = M - m0 < 256 ? M - m0 : 256;
         const size_t need = wo_narrow_workspace(rows, N, K);
@@ -1421,14 +1556,26 @@ hipError_t launch_w8a16_gemm(const void* A, const uint8_t* Wq, const void* scale
         uint16_t* op = o + (int64_t)m0 * N;
         hipError_t e;
         switch (pl.mt) {
-        case 1: e = launch_wo<1, 4>(ap, Wq, s, op, rows, N, K, pl.ks, scratch, zeros, st); break;
-        case 2: e = launch_wo<2, 4>(ap, Wq, s, op, rows, N, K, pl.ks, scratch, zeros, st); break;
-        case 4: e = launch_wo<4, 3, 2>(ap, Wq, s, op, rows, N, K, pl.ks, scratch, zeros, st); break;
-        default: e = launch_wo<8, 2, 2>(ap, Wq, s, op, rows, N, K, pl.ks, scratch, zeros, st); break;
+        case 1: e = launch_wo<1, 4, 1, BF>(ap, Wq, s, op, rows, N, K, pl.ks, scratch, zeros, st); break;
+        case 2: e = launch_wo<2, 4, 1, BF>(ap, Wq, s, op, rows, N, K, pl.ks, scratch, zeros, st); break;
+        case 4: e = launch_wo<4, 3, 2, BF>(ap, Wq, s, op, rows, N, K, pl.ks, scratch, zeros, st); break;
+        default: e = launch_wo<8, 2, 2, BF>(ap, Wq, s, op, rows, N, K, pl.ks, scratch, zeros, st); break;
         }
         if (e != hipSuccess) return e;
     }
     return hipSuccess;
 }
+
+hipError_t launch_w8a16_gemm(const void* A, const uint8_t* Wq, const void* scale, void* Out, int M, int N, int K,
+                             void* scratch, size_t scratch_bytes, const void* zeros, hipStream_t st)
+{
+    return launch_w8a16_gemm_t<false>(A, Wq, scale, Out, M, N, K, scratch, scratch_bytes, zeros, st);
+}
+hipError_t launch_w8a16_gemm_bf16(const void* A, const uint8_t* Wq, const void* scale, void* Out, int M, int N, int K,
+                                  void* scratch, size_t scratch_bytes, const void* zeros, hipStream_t st)
+{
+    return launch_w8a16_gemm_t<true>(A, Wq, scale, Out, M, N, K, scratch, scratch_bytes, zeros, st);
+}
+#undef MIXQ_WO_BF16_NAME
 
 } // namespace mixq

@@ -538,22 +538,32 @@ def int8_matrix_to_half(int_ind):
 def w8_a16_gemm(input, weight, scale):
     """EETQ/csrc/eetpy.cpp:7-19 w8_a16_gemm: fp16 [m,k] x interleaved uint8 [k,n] -> fp16 [m,n].
     m <= 4: batched GEMV; m > 4: the fpA_intB MFMA GEMM (fpA_intB_gemm_wrapper.cu:45-70), with the per-stream scratch
-    for its K split over workgroups."""
+    for its K split over workgroups.
+    MI355X extension: a bf16 ``input`` returns bf16 [m,n] = bf16(scale[n] * sum_k input[m,k] (q[k,n] - 128)) through
+    ``mixq_w8a16_gemm_forward_typed``; ``weight`` is the same image and ``scale`` stays fp16 (a bf16 ``scale`` raises ``TypeError``)."""
+    bf16 = input.dtype == torch.bfloat16
+    if bf16 and scale.dtype != torch.float16:
+        raise TypeError(f"w8_a16_gemm: scale is {scale.dtype} in a bf16 call; the column scales stay fp16 in both types")
     _dev(input, weight, scale)
     m, k = input.shape
     n = scale.numel()
-    out = torch.empty((m, n), dtype=torch.float16, device=input.device)
+    out = torch.empty((m, n), dtype=torch.bfloat16 if bf16 else torch.float16, device=input.device)
     lib = _lib.load()
-    nws = int(lib.mixq_w8a16_gemm_workspace_size(m, n, k))
+    nws = int(lib.mixq_w8a16_gemm_workspace_size_typed(m, n, k, _lib.MIXQ_TYPE_BF16) if bf16 else lib.mixq_w8a16_gemm_workspace_size(m, n, k))
     # ADVICE r2: the two-pass form (m >= 1280) wants 16 KiB + N*K*2 bytes (the fp16 image of W: ~470 MB for 28672 x 8192); parking
     # that in the never-released per-stream scratch would pin up to > 1 GB per stream.  Large requests come from the caching
     # allocator per call instead (zeroed hand-over words; freed when the call's tensors die -- stream-ordered, so safe), unless a
     # graph is being captured (then the small persistent scratch is offered and the library picks a form that fits it).
+    # (The same policy in both types; a bf16 call has no weight image, so its request stays below the limit.)
     if nws > _W8A16_PERSISTENT_SCRATCH_LIMIT and not torch.cuda.is_current_stream_capturing():
         scr = torch.empty(nws, dtype=torch.uint8, device=input.device)
         scr[:16384].zero_()
     else:
         scr = _scratch_bytes(input, min(nws, _W8A16_PERSISTENT_SCRATCH_LIMIT)) if nws else None
+    if bf16:
+        _lib.check(lib.mixq_w8a16_gemm_forward_typed(_p(input), _p(weight), _p(scale), _p(out), m, n, k, _lib.MIXQ_TYPE_BF16, _p(scr),
+                                                     scr.numel() if scr is not None else 0, _st(input)), "w8_a16_gemm")
+        return out
     _lib.check(lib.mixq_w8a16_gemm_forward_ws(_p(input), _p(weight), _p(scale), _p(out), m, n, k, _p(scr),
                                               scr.numel() if scr is not None else 0, _st(input)), "w8_a16_gemm")
     return out
