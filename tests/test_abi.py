@@ -418,3 +418,56 @@ def test_selection_table_is_the_pinned_one(lib):
     buf = ctypes.create_string_buffer(8)
     assert lib.mixq_describe_plan(32, 4096, 4096, 0, buf, 8) == 0 and len(buf.value) == 7      # truncated, terminated
     assert lib.mixq_describe_plan(0, 4096, 4096, 0, buf, 8) != 0 and lib.mixq_describe_plan(32, 4096, 4096, 0, None, 8) != 0
+
+
+def test_plan_cells_are_the_pinned_ones(lib):
+    """tests/golden/plan_cells.json (tools/plan_cells.py) holds, per plan text mixq_describe_plan prints on a fixed lattice, the cheapest
+    cell that gets it; tests/test_gpu_plan_cells.py runs every one of them through mixq_enqueue and checks every output element.  Here:
+    the file is what the library says today, EVERY text of the selection table has a cell, and a text without one is listed by name
+    with its cost -- above the bound, and never a text of the table."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, os.path.join(root, "tools", "plan_cells.py"), "--check"], capture_output=True, text=True,
+                       timeout=300, env=dict(os.environ, HIP_VISIBLE_DEVICES="", ROCR_VISIBLE_DEVICES=""))   # (the 256-CU tables, wherever this runs)
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
+    pinned = json.load(open(os.path.join(root, "tests", "golden", "plan_cells.json")))
+    table = json.load(open(os.path.join(root, "tests", "golden", "selection_table.json")))
+    texts = set()
+    for cells in table.values():
+        for v in cells.values():
+            texts |= set(v.values()) if isinstance(v, dict) else {v}
+    assert len(texts) == 30
+    have = {c["plan"] for c in pinned["cells"]}
+    assert not texts - have, f"plans of the selection table without a cell: {sorted(texts - have)}"
+    assert len(have) == len(pinned["cells"])
+    bound = pinned["lattice"]["max_MNK"]
+    assert bound == 120 * 10 ** 9
+    for c in pinned["cells"] + pinned["named"]:
+        assert c["M"] * c["N"] * c["K"] <= bound, c
+    for c in pinned["not_run"]:
+        assert c["plan"] not in texts and c["plan"] not in have, c
+        assert c["M"] * c["N"] * c["K"] > bound and c["cost"] == c["M"] * c["N"] * c["K"] + c["N"] * c["K"], c
+    # the lattice holds the ladder's edges and sizes that are no multiple of a tile
+    lat = pinned["lattice"]
+    assert set([1, 4, 5, 16, 17, 32, 33, 48, 49, 64, 65, 96, 97, 128, 129, 193, 256, 257, 385, 513, 1025, 4096]) <= set(lat["M"])
+    assert any(n % 128 == 16 for n in lat["N"]) and any(k % 256 == 128 for k in lat["K"]) and any(k % 128 == 64 for k in lat["K"])
+    # the cells named by hand have the attribute they are named for (csrc: gemm_mid_rotated_walk, skinny_runs_nontemporal, launch_cfg)
+    named = {c["name"]: c for c in pinned["named"]}
+    assert all(c["reason"] for c in named.values())
+    c = named["mid-rotated-walk"]
+    assert "copy-only waves" in c["plan"] and "1 workgroup(s) per tile" in c["plan"] and 4 <= (c["M"] + 127) // 128 <= 7
+    c = named["skinny-runs-nontemporal"]
+    assert "256-byte runs" in c["plan"] and c["image"] == 0 and c["N"] * c["K"] >= 32 << 20
+    c = named["tiles-nontemporal"]
+    assert "two-barrier 64x64" in c["plan"] and 49 <= c["M"] <= 64 and c["N"] * c["K"] >= 32 << 20
+    c = named["mid-96-scratch"]
+    tm = (c["M"] + 127) // 128
+    assert "128x96 tiles, 4 workgroup(s)" in c["plan"] and tm * ((c["N"] + 95) // 96) * 96 > tm * ((c["N"] + 127) // 128) * 128
+    scratch = 16384 + tm * ((c["N"] + 95) // 96) * 128 * 96 * 4 * 4           # hand-over words + 4 parts of every 128 x 96 int32 tile
+    assert lib.mixq_enqueue_scratch_size(c["M"], c["N"], c["K"]) == scratch
+    assert named["decode-small"]["M"] == 4 and named["decode-small"]["plan"].startswith("w8a16")
+    for a, b in (("decode-small", "decode-small-neighbour"), ("decode-large-neighbour", "skinny-runs-nontemporal")):
+        assert (named[a]["M"], named[b]["M"]) == (4, 5) and (named[a]["N"], named[a]["K"]) == (named[b]["N"], named[b]["K"])
+        assert named[a]["plan"].startswith("w8a16") and "skinny" in named[b]["plan"]
