@@ -6,6 +6,8 @@ import ctypes
 import numpy as np
 import pytest
 
+import pflavour_exact as X
+
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
@@ -51,6 +53,11 @@ def test_unpack_int4_to_int8_and_columns(oracle):
     ind = np.array([0, 1, 4095, 4094, 77, 78, 2048], np.int32)
     got = mixlib.unpack_int4_to_fp16(src, dev(ind)).cpu().numpy()
     assert np.array_equal(got, want[:, ind].astype(np.float16))
+    for R, C in ((1, 32), (33, 96)):                               # one row; rows and columns off every power of two
+        packed = rng.integers(0, 256, (R, C // 2), dtype=np.uint8)
+        ind = np.array([0, C - 1, 1, C - 2, C // 2, 0], np.int32)   # the first and the last column, a repeat
+        got = mixlib.unpack_int4_to_fp16(dev(packed), dev(ind)).cpu().numpy()
+        assert got.shape == (R, ind.size) and np.array_equal(bits(got), bits(oracle.unpack_i4(packed)[:, ind].astype(np.float16))), (R, C)
 
 
 @pytest.mark.parametrize("M,N,K,silu", [(40, 512, 1024, False), (300, 1024, 4096, False), (64, 256, 512, True),
@@ -72,8 +79,37 @@ def test_int4_fused_dequantize_bit_exact(oracle, M, N, K, silu):
     if silu:
         g, w = got.astype(np.float64), want.astype(np.float64)
         assert np.abs(g - w).max() / np.abs(w).max() < 1e-3      # __expf vs expf: not bit-pinned (as for int8)
+        X.assert_silu_rule(got, want, f"int4FusedDequantizeSilu {M}x{N}x{K}")
     else:
         assert np.array_equal(bits(got), bits(want))
+
+
+def exact_4bit_layer_follows_the_oracle_bit_for_bit(oracle, N, K, FP, prefill):
+    """A second layer whose static outlier columns are integers times a power of two per row, fed integers in those columns
+    (tests/pflavour_exact.py): the outlier product has one answer in any summation order, the rest of the 4-bit forward is exact in the
+    oracle, so the output equals oracle.mixlinear4_forward bit for bit -- at a decode batch (the packed weight stream) and at two
+    prefill sizes (the int8 kernels)."""
+    from mixq_tensorrt_llm_amd import mixlinear
+    L = X.layer4(N, K, FP, seed=N + FP)
+    cache = mixlinear.MixLibCache(inputdim=256, sigma=6, bit=4, device="cuda:0")
+    layer = mixlinear.MixLinear_GEMM.from_linear(torch.from_numpy(L["W"]), bit=4, cache=cache, dev="cuda:0",
+                                                 layer_scales=torch.from_numpy(L["scales"]), fp_features_num=FP)
+    if prefill:
+        layer.prepare_prefill()
+    qp, sc, ind, wc = oracle.mixlinear4_from_linear(L["W"], L["scales"], FP)
+    assert np.array_equal(layer.ind.cpu().numpy(), ind) and np.array_equal(ind, L["ind"])
+    assert np.array_equal(layer.q_weight.cpu().numpy(), qp) and np.array_equal(bits(layer.scale_col.cpu().numpy().reshape(-1)), bits(sc))
+    assert np.array_equal(bits(layer.weight_cache.cpu().numpy()), bits(wc))
+    for M in X.INT4_M:
+        x = X.activations4(L, M, seed=M)
+        x_ref = x.copy()
+        xt = dev(x)
+        got = layer.forward(xt, cache, True).cpu().numpy()
+        want = oracle.mixlinear4_forward(qp, sc, ind, wc, x_ref)
+        assert layer.ind.numel() == FP and np.array_equal(bits(xt.cpu().numpy()), bits(x_ref)), M
+        bad = np.argwhere(bits(got) != bits(want))
+        assert bad.size == 0, (f"exact 4-bit layer {M}x{N}x{K}, {FP} columns: {len(bad)} of {want.size} outputs differ from the oracle, first at "
+                               f"{tuple(bad[0])}: got {got[tuple(bad[0])]!r} want {want[tuple(bad[0])]!r}")
 
 
 def test_mixlinear_4bit_from_linear_and_forward(oracle):
@@ -103,6 +139,7 @@ def test_mixlinear_4bit_from_linear_and_forward(oracle):
     # 4-bit weights + 4-bit activations are coarse, but the result must still track the fp product
     ref = x.astype(np.float64) @ W.astype(np.float64).T
     assert np.abs(g - ref).max() / np.abs(ref).max() < 0.35
+    exact_4bit_layer_follows_the_oracle_bit_for_bit(oracle, N, K, FP, prefill=False)
 
 
 def test_fused_norm_4bit_producer(oracle):
@@ -164,6 +201,7 @@ def test_int4_weight_stream_bit_exact(oracle, M, N, K, silu):
     if silu:
         g, w = got.astype(np.float64), want.astype(np.float64)
         assert np.abs(g - w).max() / np.abs(w).max() < 1e-3      # __expf vs expf: not bit-pinned (as for int8)
+        X.assert_silu_rule(got, want, f"int4 weight stream SiLU {M}x{N}x{K}")
     else:
         assert np.array_equal(bits(got), bits(want))
     # the route this replaces (both operands unpacked to int8 in a workspace, then the int8 kernels): same bits, SiLU included
@@ -201,6 +239,8 @@ def test_int4_weight_stream_bit_exact(oracle, M, N, K, silu):
     want0 = oracle.dequant_epilogue(oracle.gemm_s8s8s32(a, b), sa, sb, C=None, silu=silu)
     if not silu:
         assert np.array_equal(bits(D2.cpu().numpy()), bits(want0))
+    else:
+        X.assert_silu_rule(D2.cpu().numpy(), want0, f"int4 weight stream SiLU, no addend {M}x{N}x{K}")
 
 
 def test_int4_prefill_with_the_weight_widened_once(oracle):
@@ -244,6 +284,7 @@ def test_mixlinear_4bit_decode_batch_and_prefill_agree_with_the_oracle(oracle):
         want = oracle.mixlinear4_forward(qp, sc, ind, wc, x.copy())
         g, w = got.astype(np.float64), want.astype(np.float64)
         assert np.abs(g - w).max() / np.abs(w).max() < 1e-3, M
+    exact_4bit_layer_follows_the_oracle_bit_for_bit(oracle, N, K, FP, prefill=True)
 
 
 @pytest.mark.parametrize("silu", [False, True])
@@ -306,5 +347,6 @@ def test_int4_linear_forward_is_quant_then_gemm_in_one_call(oracle, M, N, K, sil
     if silu:
         ok = np.isfinite(w)
         assert np.abs(g[ok] - w[ok]).max() / max(np.abs(w[ok]).max(), 1e-30) < 1e-3
+        X.assert_silu_rule(got.cpu().numpy(), want, f"int4_linear_forward SiLU {M}x{N}x{K}")
     else:
         assert np.array_equal(bits(got.cpu().numpy()), bits(want))

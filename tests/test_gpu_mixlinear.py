@@ -3,6 +3,9 @@ through the C ABI, against the oracle's numpy restatement of the same state mach
 import numpy as np
 import pytest
 
+import pflavour_exact
+from conftest import assert_elementwise
+
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
@@ -61,6 +64,7 @@ def test_outlier_product_any_width(oracle, odd_o):
     w = (rng.standard_normal((96, odd_o)) * 0.02).astype(np.float16)
     got = mixlinear.outlier_product(dev(a), dev(w)).cpu().numpy()
     assert rel_err(got, oracle.gemm_fp16(a, w)) < REL_TOL
+    assert_elementwise(got, oracle.gemm_fp16(a, w), pflavour_exact.side_slack(a, w), f"outlier_product 70x96x{odd_o}")
 
 
 def make_layer(rng, N, K, bias):
@@ -162,6 +166,7 @@ def test_mixlinear_arch9_takes_the_reference_sm90_route(oracle, with_outliers):
             want_g = oracle.dequantization_silu(acc, cache.x_scale[:M].cpu().numpy(), gate.scale_col.cpu().numpy(), yg)
             d = np.abs(g.astype(np.float64) - want_g.astype(np.float64))
             assert (d <= 2.0 ** -10 * np.maximum(np.abs(want_g.astype(np.float64)), 2.0 ** -14) + 1e-7).all()   # SiLU: <= 1 ulp (conftest bounds)
+            pflavour_exact.assert_silu_rule(g, want_g, f"arch == 9 dequantizeInt8Silu, outliers {with_outliers}")
     assert rel_err(outs[9], outs[0]) < REL_TOL
 
 

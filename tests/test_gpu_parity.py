@@ -383,6 +383,8 @@ def test_fp16_side_gemm(oracle):
                                     ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
     assert rc == 0
     assert rel_err(out.cpu().numpy(), oracle.gemm_fp16(fa, fw)) < REL_TOL
+    import pflavour_exact
+    assert_elementwise(out.cpu().numpy(), oracle.gemm_fp16(fa, fw), pflavour_exact.side_slack(fa, fw), f"gemm_fp16 {M}x{N}x{O}")
 
 
 # --------------------------------------------------------------------------- the whole operator --------
