@@ -366,6 +366,29 @@ MIXQ_API int mixq_gemm_mixed_typed(const int8_t* qA, const int8_t* W, const void
 MIXQ_API int mixq_gemm_mixed_act_typed(const int8_t* qA, const int8_t* W, const void* sA, const void* sW, const void* fpA, const void* fpW,
                                        const void* mul, void* Out, int M, int N, int K, int O, int epilogue, int qa_layout, int type,
                                        void* scratch, size_t scratch_bytes, void* stream);
+/* The gate and the up projection of an MLP as ONE launch with SiLU(gate) x up in its epilogue (MI355X extension; the reference launches
+ * the two projections separately and serving stacks keep them as one gate_up_proj weight).  `gate` and `up` share K, N (N % 16 == 0), the
+ * outlier index set and have no bias; they are MERGED into one layer of 2 N rows, interleaved in blocks of 8 rows -- the one layout of
+ * every kernel family (pack.merge_gate_up builds it at load time; the checkpoint format is unchanged):
+ *     merged row r(n) = 16 * (n / 8) + (n % 8)    holds gate row n
+ *     merged row r(n) + 8                         holds up   row n
+ * applied alike to W2 int8 [2N, K], sW2 fp16 [2N] and fpW2 [2N, O] (type T); the outlier columns are shared.  Gate column n and up column n
+ * of the (M, 2N, K) GEMM then belong to the same lane in every family on the 32 x 32 MFMA (column quads 8 apart) and to lanes l, l ^ 32 of
+ * the skinny kernel, which hands u across lanes.  Per element, T the call's type, P the in-kernel outlier product rounded to T:
+ *     v_g = fma(float(acc[m, r(n)]),     float(sW2[r(n)])     * float(sA[m]), float(P[m, r(n)]))
+ *     v_u = fma(float(acc[m, r(n) + 8]), float(sW2[r(n) + 8]) * float(sA[m]), float(P[m, r(n) + 8]))
+ *     g   = T_rn(v_g / (1 + expf(-v_g))),   u = T_rn(v_u)
+ *     Out[m, n] = T_rn(float(g) * float(u))                              Out is [M, N], row stride N
+ * -- bit for bit mixq_gemm_mixed_typed for u followed by mixq_gemm_mixed_act_typed(epilogue 3, mul = u) on the unmerged layers, without
+ * the [M, N] round trip of u and without the second pass over qA, sA and fpA.  N is the OUTPUT width: kernel, K split, scratch
+ * (mixq_gemm_scratch_size(M, 2 N, K)) and the name mixq_debug_last_gemm_kernel reports are those of the plain call on (M, 2 N, K).
+ * Checks, in this order: MIXQ_E_TYPE; MIXQ_E_BADARG (a null operand, a negative size, a bad qa_layout); MIXQ_E_SHAPE (N % 16, K % 16,
+ * O % 8, O > 128, fragment-major where the skinny kernel does not serve (M, 2 N, K)); MIXQ_E_ALIGN (as the typed entry).  M == 0 or N == 0
+ * returns MIXQ_OK without touching the device.  No bias, no addend, no peer writes.  Asynchronous, no allocation, capturable; scratch as
+ * mixq_gemm_mixed_scratch (may be NULL); every buffer is used at exactly its declared size. */
+MIXQ_API int mixq_gemm_mixed_gate_up_typed(const int8_t* qA, const int8_t* W2, const void* sA, const void* sW2, const void* fpA,
+                                           const void* fpW2, void* Out, int M, int N, int K, int O, int qa_layout, int type,
+                                           void* scratch, size_t scratch_bytes, void* stream);
 /* MixLinear_GEMM.forward (MixQ/src/mixquant/modules/linear.py:163-286, bit = 8, static outlier set) as ONE call and TWO
  * launches: the reference makes four mixlib calls per linear here (ExtractOutliersAndSetToZeros, FindRowScale, torch.mm on the
  * outliers, int8FusedDequantize); a decode step is host-bound on those calls long before it is GPU-bound
@@ -696,7 +719,7 @@ MIXQ_API const char* mixq_version(void);
  * Revision 5 adds entries only (mixq_enqueue_bias, mixq_enqueue_tp_bias, mixq_gemm_mixed_bias; later, still 5: mixq_add_rmsnorm*,
  * mixq_rmsnorm_typed, mixq_rmsnorm_extract_quant_typed, mixq_gemm_mixed_typed, mixq_gemm_mixed_act_typed, mixq_quant_extract_typed,
  * mixq_find_outliers_typed, mixq_dequant_weight_columns_typed, mixq_mixlinear_forward_typed, mixq_w8a16_gemm_workspace_size_typed,
- * mixq_w8a16_gemm_forward_typed). */
+ * mixq_w8a16_gemm_forward_typed, mixq_gemm_mixed_gate_up_typed). */
 #define MIXQ_ABI_VERSION 5
 MIXQ_API int mixq_abi_version(void);
 MIXQ_API const char* mixq_error_string(int code);

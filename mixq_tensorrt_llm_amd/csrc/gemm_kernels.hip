@@ -401,6 +401,34 @@ __global__ __launch_bounds__(WAVES_M* WAVES_N* KG * 64) void gemm_w8a8o16_kernel
                     P = mfma32_o<epi_bf16(EPI)>(xf, yf, P);
                 }
             }
+            if constexpr (epi_gate_up(EPI)) { // merged gate / up: this lane's quads 2 gp and 2 gp + 1 are the gate and the up columns of output quad gp
+                constexpr bool BF = epi_bf16(EPI);
+                if (m < p.M) {
+#pragma unroll
+                    for (int gp = 0; gp < 2; ++gp) {
+                        const int nb = nb0 + 16 * gp; // (GEMM column of the gate quad; N % 32 == 0: a 32-column block is inside or outside as a whole)
+                        if (nb < p.N) {
+                            const uint2 sg = sw_pre[i][2 * gp], su = sw_pre[i][2 * gp + 1];
+                            const uint16_t sgh[4] = {(uint16_t)(sg.x & 0xffffu), (uint16_t)(sg.x >> 16), (uint16_t)(sg.y & 0xffffu), (uint16_t)(sg.y >> 16)};
+                            const uint16_t suh[4] = {(uint16_t)(su.x & 0xffffu), (uint16_t)(su.x >> 16), (uint16_t)(su.y & 0xffffu), (uint16_t)(su.y >> 16)};
+                            uint16_t oh[4];
+#pragma unroll
+                            for (int e = 0; e < 4; ++e) {
+                                const float cg = has_outliers ? o2f<BF>(f2o_bits_of_f32_result<BF>(P[8 * gp + e])) : 0.f;
+                                const float cu = has_outliers ? o2f<BF>(f2o_bits_of_f32_result<BF>(P[8 * gp + 4 + e])) : 0.f;
+                                const float vg = __builtin_fmaf((float)acc[i][j][8 * gp + e], h2f(sgh[e]) * sa_pre[j], cg);
+                                const float vu = __builtin_fmaf((float)acc[i][j][8 * gp + 4 + e], h2f(suh[e]) * sa_pre[j], cu);
+                                oh[e] = gate_up_bits<BF>(vg, vu);
+                            }
+                            uint2 o;
+                            o.x = (unsigned)oh[0] | ((unsigned)oh[1] << 16);
+                            o.y = (unsigned)oh[2] | ((unsigned)oh[3] << 16);
+                            *reinterpret_cast<uint2*>(static_cast<uint16_t*>(p.D) + (int64_t)m * p.n_out + gate_up_col(nb)) = o;
+                        }
+                    }
+                }
+                continue;
+            }
             if (m < p.M) {
                 const float sa = sa_pre[j];
 #pragma unroll

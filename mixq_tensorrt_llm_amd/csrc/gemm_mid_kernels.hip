@@ -243,6 +243,29 @@ __device__ __forceinline__ void mid_finish(const GemmParams& p, char* smem, v16i
                 }
             }
         }
+        if constexpr (epi_gate_up(EPI)) { // merged gate / up: the half tile's quad 0 holds the gate columns, quad 1 (8 columns on) their up columns
+            constexpr bool BF = epi_bf16(EPI);
+            if (m < p.M && nb0 < p.N) { // (N % 32 == 0: a 32-column block is inside or outside as a whole)
+                const uint2 sg = pre.sw[k][0], su = pre.sw[k][1];
+                const uint16_t sgh[4] = {(uint16_t)(sg.x & 0xffffu), (uint16_t)(sg.x >> 16), (uint16_t)(sg.y & 0xffffu), (uint16_t)(sg.y >> 16)};
+                const uint16_t suh[4] = {(uint16_t)(su.x & 0xffffu), (uint16_t)(su.x >> 16), (uint16_t)(su.y & 0xffffu), (uint16_t)(su.y >> 16)};
+                uint16_t oh[4];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const float pg = t.gh ? P[8 + e] : P[e], pu = t.gh ? P[12 + e] : P[4 + e];
+                    const float cg = has_outliers ? o2f<BF>(f2o_bits_of_f32_result<BF>(pg)) : 0.f;
+                    const float cu = has_outliers ? o2f<BF>(f2o_bits_of_f32_result<BF>(pu)) : 0.f;
+                    const float vg = __builtin_fmaf((float)fin[k][e], h2f(sgh[e]) * pre.sa[k], cg);
+                    const float vu = __builtin_fmaf((float)fin[k][4 + e], h2f(suh[e]) * pre.sa[k], cu);
+                    oh[e] = gate_up_bits<BF>(vg, vu);
+                }
+                uint2 o;
+                o.x = (unsigned)oh[0] | ((unsigned)oh[1] << 16);
+                o.y = (unsigned)oh[2] | ((unsigned)oh[3] << 16);
+                *reinterpret_cast<uint2*>(static_cast<uint16_t*>(p.D) + (int64_t)m * p.n_out + gate_up_col(nb0)) = o;
+            }
+            continue;
+        }
         if (m < p.M) {
             const float sa = pre.sa[k];
 #pragma unroll

@@ -464,6 +464,8 @@ hipError_t launch_gemm(const GemmParams& p, int epi, hipStream_t st, const GemmP
     if (p.a_frag < 0 || p.a_frag > 2) return hipErrorInvalidValue;
     if (epi_bias(epi) && (p.bias == nullptr || p.Y != nullptr)) return hipErrorInvalidValue; // (no bias form with an addend)
     if (epi_bf16(epi) && (p.Y != nullptr || p.O > 128)) return hipErrorInvalidValue; // (bf16 calls: enqueue's single LDS pass of outliers only)
+    if (epi_gate_up(epi) ? (p.n_out <= 0 || p.N != 2 * p.n_out || p.n_out % 16 != 0 || p.Y != nullptr || p.O > 128) : p.n_out != 0)
+        return hipErrorInvalidValue; // (merged gate / up: D is [M, N / 2], whole 16-row blocks of the merged weight, no addend)
     const GemmPlan pl = planned ? *planned : plan_gemm(p, epi);
     if (p.a_frag == 1 && pl.family != GEMM_SKINNY) return hipErrorInvalidValue; // (only the skinny kernel reads that image)
     if (p.a_frag == 2 && !(epi == EPI_DEQUANT && pl.family == GEMM_PP)) return hipErrorInvalidValue; // (only the plain 256 x 256 kernel reads that one)

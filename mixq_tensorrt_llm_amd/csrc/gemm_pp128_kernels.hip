@@ -358,6 +358,41 @@ __global__ __launch_bounds__(512) void gemm_w8a8o16_pp128_kernel(const GemmParam
     if (HAS_Y) fetch(p.Y, 0, ypre);
     if (HAS_MUL) fetch(p.Mul, 0, mpre);
     auto dequant = [&](int i, int j, const v16f& P) __attribute__((always_inline)) {
+        if constexpr (epi_gate_up(EPI)) { // merged gate / up: quads 2 gp and 2 gp + 1 are the gate and the up columns of output quad gp; the window
+                                          // row holds the block's 32 OUTPUT columns (64 bytes: chunks 2 i + gp), same pitch and swizzle
+            constexpr bool BF = epi_bf16(EPI);
+#pragma unroll
+            for (int gp = 0; gp < 2; ++gp) {
+                unsigned ow[2];
+#pragma unroll
+                for (int e2 = 0; e2 < 4; e2 += 2) {
+                    float v[2][2]; // [gate | up][element]
+#pragma unroll
+                    for (int h = 0; h < 2; ++h) {
+                        const int g = 2 * gp + h;
+                        const unsigned sw2 = e2 ? swq[i][g].y : swq[i][g].x;
+                        const v2f s2 = v2f{h2f((uint16_t)(sw2 & 0xffffu)), h2f((uint16_t)(sw2 >> 16))} * sa[j]; // exact: fp16 x fp16 products
+                        v2f c2 = v2f{0.f, 0.f};
+                        if (HAS_O && BF) {
+                            const unsigned pb = __builtin_bit_cast(unsigned, f2bf2_of_f32_results(P[4 * g + e2], P[4 * g + e2 + 1]));
+                            c2 = v2f{bf2f((uint16_t)(pb & 0xffffu)), bf2f((uint16_t)(pb >> 16))};
+                        } else if (HAS_O) {
+                            const v2h p16 = f2h2(P[4 * g + e2], P[4 * g + e2 + 1]);
+                            c2 = v2f{(float)p16[0], (float)p16[1]};
+                        }
+                        v[h][0] = __builtin_fmaf((float)acc[i][j][4 * g + e2], s2[0], c2[0]);
+                        v[h][1] = __builtin_fmaf((float)acc[i][j][4 * g + e2 + 1], s2[1], c2[1]);
+                    }
+                    const v2h g16 = f2o2_of_f32_results<BF>(silu_f32(v[0][0]), silu_f32(v[0][1]));
+                    const v2h u16 = f2o2_of_f32_results<BF>(v[1][0], v[1][1]);
+                    const v2h o16 = omul2<BF>(g16, __builtin_bit_cast(unsigned, u16));
+                    __builtin_memcpy(&ow[e2 >> 1], &o16, 4);
+                }
+                const int c = i * 2 + gp; // 16-byte chunk of the 64-byte output row
+                *reinterpret_cast<uint2*>(wstg + wrow + ((c ^ (lr & 7)) << 4)) = uint2{ow[0], ow[1]};
+            }
+            return;
+        }
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
             const uint2 swb = swq[i][g];
@@ -413,6 +448,21 @@ __global__ __launch_bounds__(512) void gemm_w8a8o16_pp128_kernel(const GemmParam
     const bool n_ok = n0 + wn * 64 + (lane & 7) * 8 < p.N;
     const bool interior = m0 + BM <= p.M && n0 + BN <= p.N; // wave-uniform: no store predicates needed
     auto flush = [&](int j) __attribute__((always_inline)) {
+        if constexpr (epi_gate_up(EPI)) { // 32 rows x 64 bytes of [M, n_out]: two stores of 16 rows x 64-byte segments
+            const int rr = lane >> 2, ch = lane & 3; // row inside the 16, 16-byte chunk of the segment
+            const int ncol = ((n0 + wn * 64) >> 1) + ch * 8;
+#pragma unroll
+            for (int q = 0; q < 2; ++q) {
+                const int rl = q * 16 + rr;
+                uint4 v = *reinterpret_cast<const uint4*>(wstg + rl * 128 + ((ch ^ (rl & 7)) << 4));
+                if (rr & 8) v = uint4{v.z, v.w, v.x, v.y}; // rows with bit 3 set hold their 8-B halves swapped
+                const int m = m0 + wm * 64 + j * 32 + rl;
+                const v4i vv = {(int)v.x, (int)v.y, (int)v.z, (int)v.w};
+                if (interior || (ncol < p.n_out && m < p.M))
+                    __builtin_nontemporal_store(vv, reinterpret_cast<v4i*>(static_cast<uint16_t*>(p.D) + (int64_t)m * p.n_out + ncol));
+            }
+            return;
+        }
         uint4 v[4];
 #pragma unroll
         for (int q = 0; q < 4; ++q) v[q] = *reinterpret_cast<const uint4*>(wstg + q * 1024 + rd);
@@ -467,7 +517,7 @@ template <int EPI>
 static hipError_t launch_pp128_epi(const GemmParams& p, hipStream_t st)
 {
     if (p.O > 0) return launch_pp128_cfg<EPI, true, false>(p, st); // the API never passes both an addend and outliers
-    if constexpr (epi_bias(EPI) || epi_bf16(EPI)) {
+    if constexpr (epi_bias(EPI) || epi_bf16(EPI) || epi_gate_up(EPI)) {
         if (p.Y != nullptr) return hipErrorInvalidValue; // (the bias and bf16 epilogues take no addend)
     } else if (p.Y != nullptr) return launch_pp128_cfg<EPI, false, true>(p, st);
     return launch_pp128_cfg<EPI, false, false>(p, st);

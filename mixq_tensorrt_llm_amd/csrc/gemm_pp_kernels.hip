@@ -110,6 +110,7 @@ __global__ __launch_bounds__(512) void gemm_w8a8o16_pp_kernel(const GemmParams p
                   "the peer-write epilogue exists for the plain kernel");
     static_assert(EPI != EPI_DEQUANT_BIAS || (!HAS_Y && ABL == 0), "the bias epilogue takes no addend y");
     static_assert(!epi_bf16(EPI) || (!HAS_Y && ABL == 0 && !TP), "the bf16 epilogues take no addend y and no peer writes");
+    static_assert(!epi_gate_up(EPI) || (!HAS_Y && ABL == 0 && !TP), "the merged gate / up epilogue takes no addend y and no peer writes");
     constexpr bool BF = epi_bf16(EPI); // (bf16 call: sA, the outlier operands, P and D in bf16)
     constexpr int S = SPLITK ? SPLITK : 1; // workgroups per tile
     constexpr int PJ = S >= 4 ? 1 : 4 / S; // 32-row m tiles (per wave) this workgroup finishes
@@ -621,7 +622,9 @@ __global__ __launch_bounds__(512) void gemm_w8a8o16_pp_kernel(const GemmParams p
     constexpr bool MUL_LATE = epi_has_mul(EPI) && BF;
     constexpr bool HAS_MUL = epi_has_mul(EPI) && !MUL_LATE;
     // (bf16 SiLU builds) the next tile's outlier product is issued behind this tile's dequant, not under it: 16 registers less across the SiLU
-    constexpr bool P_BEHIND = epi_has_silu(EPI) && BF;
+    // (merged gate / up with K split over two workgroups, whose share is four tiles per wave next to the hand-over state: the same, or it spills like
+    //  the other builds of that form)
+    constexpr bool P_BEHIND = (epi_has_silu(EPI) && BF) || (epi_gate_up(EPI) && SPLITK == 2 && HAS_O);
     uint2 yq[2][4], mq[2][4];
     uint4 ypre[4], mpre[4];
 #pragma unroll
@@ -656,6 +659,47 @@ __global__ __launch_bounds__(512) void gemm_w8a8o16_pp_kernel(const GemmParams p
     if (HAS_MUL) fetch(p.Mul, 0, mpre);
     // dequant of tile (i, j) with its side product P -> 4 quads (4 consecutive n of row m each) -> window
     auto dequant = [&](int i, int j, const v16f& P) __attribute__((always_inline)) {
+        if constexpr (epi_gate_up(EPI)) { // merged gate / up: quads 2 gp and 2 gp + 1 are the gate and the up columns of output quad gp; the window
+                                          // row holds the block's 32 OUTPUT columns (64 bytes: chunks 2 i + gp), same pitch and swizzle
+#pragma unroll
+            for (int gp = 0; gp < 2; ++gp) {
+                unsigned ow[2];
+#pragma unroll
+                for (int e2 = 0; e2 < 4; e2 += 2) {
+                    float v[2][2]; // [gate | up][element]
+#pragma unroll
+                    for (int h = 0; h < 2; ++h) {
+                        const int g = 2 * gp + h;
+                        const unsigned sw2 = e2 ? swq[i][g].y : swq[i][g].x;
+                        const v2f s2 = v2f{h2f((uint16_t)(sw2 & 0xffffu)), h2f((uint16_t)(sw2 >> 16))} * sa_cur; // exact: fp16 x fp16 products
+                        v2f c2 = v2f{0.f, 0.f};
+                        if (HAS_O && BF) {
+                            const unsigned pb = __builtin_bit_cast(unsigned, f2bf2_of_f32_results(P[4 * g + e2], P[4 * g + e2 + 1]));
+                            c2 = v2f{bf2f((uint16_t)(pb & 0xffffu)), bf2f((uint16_t)(pb >> 16))};
+                        } else if (HAS_O) {
+                            const v2h p16 = f2h2(P[4 * g + e2], P[4 * g + e2 + 1]);
+                            c2 = v2f{(float)p16[0], (float)p16[1]};
+                        }
+                        v[h][0] = __builtin_fmaf((float)acc[i][j][4 * g + e2], s2[0], c2[0]);
+                        v[h][1] = __builtin_fmaf((float)acc[i][j][4 * g + e2 + 1], s2[1], c2[1]);
+                    }
+                    const v2h g16 = f2o2_of_f32_results<BF>(silu_f32(v[0][0]), silu_f32(v[0][1]));
+                    const v2h u16 = f2o2_of_f32_results<BF>(v[1][0], v[1][1]);
+                    const v2h o16 = omul2<BF>(g16, __builtin_bit_cast(unsigned, u16));
+                    __builtin_memcpy(&ow[e2 >> 1], &o16, 4);
+                }
+                if (S == 8) { // a single 32x32 tile per wave: 8-byte stores straight from the accumulator layout
+                    const int m = m0 + wm * 128 + jmap(j) * 32 + lr;
+                    const int n = n0 + wn * 64 + imap(i) * 32 + 4 * lh + 16 * gp; // (GEMM column of the gate quad)
+                    if (m < p.M && n < p.N)
+                        *reinterpret_cast<uint2*>(static_cast<uint16_t*>(p.D) + (int64_t)m * p.n_out + gate_up_col(n)) = uint2{ow[0], ow[1]};
+                    continue;
+                }
+                const int c = i * 2 + gp; // 16-byte chunk of the 64-byte output row
+                *reinterpret_cast<uint2*>(wstg + wrow + ((c ^ (lr & 7)) << 4)) = uint2{ow[0], ow[1]};
+            }
+            return;
+        }
         uint2 bq[4];
         if constexpr (epi_bias(EPI)) {
             int bcol = n0 + wn * 64 + imap(i) * 32 + 4 * lh;
@@ -737,6 +781,23 @@ __global__ __launch_bounds__(512) void gemm_w8a8o16_pp_kernel(const GemmParams p
     const int64_t tp_wave = TP ? ((int64_t)(m0 + wm * 128) * p.tp.ldd + n0 + wn * 64) * 2 : 0;
     const unsigned tp_lane = TP ? ((unsigned)(lane >> 3) * (unsigned)p.tp.ldd + (lane & 7) * 8) * 2 : 0u;
     auto flush = [&](int j) __attribute__((always_inline)) {
+        if constexpr (epi_gate_up(EPI)) { // 32 rows x 64 bytes of [M, n_out]: two stores of 16 rows x 64-byte segments
+            unsigned ln = (unsigned)lane;
+            asm volatile("" : "+v"(ln)); // (re-derived, not carried across the block: see below)
+            const int rr = (int)(ln >> 2), ch = (int)(ln & 3); // row inside the 16, 16-byte chunk of the segment
+            const int ncol = ((n0 + wn * 64) >> 1) + ch * 8;
+#pragma unroll
+            for (int q = 0; q < 2; ++q) {
+                const int rl = q * 16 + rr;
+                uint4 v = *reinterpret_cast<const uint4*>(wstg + rl * 128 + ((ch ^ (rl & 7)) << 4));
+                if (rr & 8) v = uint4{v.z, v.w, v.x, v.y}; // rows with bit 3 set hold their 8-B halves swapped
+                const int m = m0 + wm * 128 + jmap(j) * 32 + rl;
+                const v4i vv = {(int)v.x, (int)v.y, (int)v.z, (int)v.w};
+                if (interior || (ncol < p.n_out && m < p.M))
+                    __builtin_nontemporal_store(vv, reinterpret_cast<v4i*>(static_cast<uint16_t*>(p.D) + (int64_t)m * p.n_out + ncol));
+            }
+            return;
+        }
         // (the two per-lane offsets of the flush are re-derived from an opaque copy of the lane id instead of living in
         //  registers across the side GEMM + dequant of the block: that was the last value the epilogue spilled)
         unsigned ln = (unsigned)lane;
@@ -941,7 +1002,7 @@ static hipError_t launch_pp_epi(const GemmParams& p, hipStream_t st)
 {
     const bool has_o = p.O > 0, has_y = p.Y != nullptr;
     if (has_o) return launch_pp_cfg<EPI, true, false>(p, st); // the API never passes both an addend and outliers
-    if constexpr (epi_bias(EPI) || epi_bf16(EPI)) {
+    if constexpr (epi_bias(EPI) || epi_bf16(EPI) || epi_gate_up(EPI)) {
         if (has_y) return hipErrorInvalidValue;
     } else if (has_y) return launch_pp_cfg<EPI, false, true>(p, st);
     return launch_pp_cfg<EPI, false, false>(p, st);
@@ -1085,7 +1146,7 @@ template <int EPI, int SPLITK>
 static hipError_t launch_pp_splitk_epi(const GemmParams& p, hipStream_t st)
 {
     if (p.O > 0) return launch_pp_splitk_cfg<EPI, true, false, SPLITK>(p, st);
-    if constexpr (epi_bias(EPI) || epi_bf16(EPI)) {
+    if constexpr (epi_bias(EPI) || epi_bf16(EPI) || epi_gate_up(EPI)) {
         if (p.Y != nullptr) return hipErrorInvalidValue;
     } else if (p.Y != nullptr) return launch_pp_splitk_cfg<EPI, false, true, SPLITK>(p, st);
     return launch_pp_splitk_cfg<EPI, false, false, SPLITK>(p, st);

@@ -84,7 +84,9 @@ __global__ __launch_bounds__(KW * 64) void gemm_skinny_kernel(const GemmParams p
             }
         }
         psa = p.sA[min(fm, p.M - 1)];
-        psw = *reinterpret_cast<const uint2*>(p.sW + min(fnb, p.N - 4));
+        // (merged gate / up: the weight scales are requested in the epilogue -- the two registers through the main loop cost the 17..32-row forms
+        //  half their occupancy, 240 + 16 -> 242 + 16 of 256, as the bias would)
+        if constexpr (!epi_gate_up(EPI)) psw = *reinterpret_cast<const uint2*>(p.sW + min(fnb, p.N - 4));
     }
 
     const v4i zero4 = {0, 0, 0, 0};
@@ -100,7 +102,9 @@ __global__ __launch_bounds__(KW * 64) void gemm_skinny_kernel(const GemmParams p
     //     first MFMA, so the compiler's counted `vmcnt(n)` lets step u multiply while steps u+1.. are still on their way.
     // (Round 2's ablations of the old form, 4096 x 4096, GEMM only, us: M = 32 full 7.8 | no qA loads 4.7 | no weight loads
     //  5.9 | no loads at all 4.6.)
-    constexpr int STEPS = (MT <= 2 && NT == 1) ? 16 : 8; // k-steps per batch: (NT + MT) x STEPS x 4 fragment registers
+    // (merged gate / up on 16 K-split waves, measurement knob only: 128 registers per lane -- short batches, or the build spills as its twins do)
+    constexpr int STEPS = epi_gate_up(EPI) && KW == 16 ? (MT <= 2 ? 4 : 2)
+                                                       : (MT <= 2 && NT == 1) ? 16 : 8; // k-steps per batch: (NT + MT) x STEPS x 4 fragment registers
     const bool ktail = (p.K & 63) != 0;     // the row's last step is partial (K % 16 == 0 is checked on the host)
     const int koff_last = p.K - 16;
     auto do_steps = [&](int s0, int cnt, auto full_tag) __attribute__((always_inline)) {
@@ -268,6 +272,32 @@ __global__ __launch_bounds__(KW * 64) void gemm_skinny_kernel(const GemmParams p
                 }
                 P = mfma16_o<epi_bf16(EPI)>(xf, yf, P);
             }
+        }
+        if constexpr (epi_gate_up(EPI)) { // merged gate / up: of the tile's 16 GEMM columns lanes 0-31 hold the 8 gate columns, lanes 32-63 their up columns
+            // (lane l's partner is l ^ 32).  Every lane dequantises its own four values (clamped loads: all 64 lanes take part in the swap), the up
+            // lanes hand their rounded u across, the gate lanes multiply and store 4 of the tile's 8 output columns.
+            constexpr bool BF = epi_bf16(EPI);
+            const float sa = o2f<BF>(tt == wave ? psa : p.sA[min(m, p.M - 1)]);
+            const uint2 swb = *reinterpret_cast<const uint2*>(p.sW + min(nb, p.N - 4));
+            const uint16_t swh[4] = {(uint16_t)(swb.x & 0xffffu), (uint16_t)(swb.x >> 16), (uint16_t)(swb.y & 0xffffu), (uint16_t)(swb.y >> 16)};
+            const bool up = lq >= 2;
+            uint16_t oh[4];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const float c = p.O > 0 ? o2f<BF>(f2o_bits_of_f32_result<BF>(P[e])) : 0.f;
+                float v = __builtin_fmaf((float)a[e], h2f(swh[e]) * sa, c);
+                if (!up) v = silu_f32(v);
+                oh[e] = f2o_bits_of_f32_result<BF>(v);
+            }
+            const unsigned mine0 = (unsigned)oh[0] | ((unsigned)oh[1] << 16), mine1 = (unsigned)oh[2] | ((unsigned)oh[3] << 16);
+            const unsigned u0 = (unsigned)__shfl_xor((int)mine0, 32, 64), u1 = (unsigned)__shfl_xor((int)mine1, 32, 64);
+            if (!up && m < p.M && nb < p.N) {
+                uint2 o;
+                o.x = (unsigned)omul_bits<BF>(oh[0], (uint16_t)(u0 & 0xffffu)) | ((unsigned)omul_bits<BF>(oh[1], (uint16_t)(u0 >> 16)) << 16);
+                o.y = (unsigned)omul_bits<BF>(oh[2], (uint16_t)(u1 & 0xffffu)) | ((unsigned)omul_bits<BF>(oh[3], (uint16_t)(u1 >> 16)) << 16);
+                *reinterpret_cast<uint2*>(static_cast<uint16_t*>(p.D) + (int64_t)m * p.n_out + gate_up_col(nb)) = o;
+            }
+            continue;
         }
         if (m < p.M && nb < p.N) {
             const float sa = o2f<epi_bf16(EPI)>(tt == wave ? psa : p.sA[m]);

@@ -841,6 +841,7 @@ struct MixedCall {
     const void* bias;                // the layer's [N] bias of the call's type (the same kernel, one add in its epilogue), or null
     int act;                         // 0 | EPI_DEQUANT_SILU | EPI_DEQUANT_SILU_MUL with mul, its [M, N] multiplicand of the call's type; never with a bias
     const void* mul;
+    bool gate_up;                    // W, sW, fpW are the merged gate / up layer of N rows, Out is [M, N / 2] (EPI_GATE_UP): no bias, no act, O <= 128
     const mixq::GemmPlan* plan;      // mixq_enqueue has planned this call already (O == kNumOutliers, scratch sized by gemm_scratch_bytes), or null
 };
 
@@ -854,8 +855,9 @@ static MixedCall mixed_call(const int8_t* qA, const int8_t* W, const void* sA, c
 }
 
 // the epilogue of a mixed GEMM with 128 outlier columns at most
-static int mixed_epi(bool bias, bool bf16, int act)
+static int mixed_epi(bool bias, bool bf16, int act, bool gate_up = false)
 {
+    if (gate_up) return bf16 ? mixq::EPI_GATE_UP_BF16 : mixq::EPI_GATE_UP;
     if (act == mixq::EPI_DEQUANT_SILU) return bf16 ? mixq::EPI_DEQUANT_SILU_BF16 : mixq::EPI_DEQUANT_SILU;
     if (act == mixq::EPI_DEQUANT_SILU_MUL) return bf16 ? mixq::EPI_DEQUANT_SILU_MUL_BF16 : mixq::EPI_DEQUANT_SILU_MUL;
     return bf16 ? (bias ? mixq::EPI_DEQUANT_BIAS_BF16 : mixq::EPI_DEQUANT_BF16) : (bias ? mixq::EPI_DEQUANT_BIAS : mixq::EPI_DEQUANT);
@@ -888,10 +890,11 @@ static int gemm_mixed_impl(const MixedCall& c)
         p.fpA = static_cast<const uint16_t*>(c.fpA), p.fpW = static_cast<const uint16_t*>(c.fpW), p.O = c.O;
         p.bias = static_cast<const uint16_t*>(c.bias);
         p.Mul = static_cast<const uint16_t*>(c.mul);
+        p.n_out = c.gate_up ? c.N / 2 : 0;
         g_last_gemm_bf16.store(c.bf16, std::memory_order_relaxed);
-        return hip_rc(mixq::launch_gemm(p, mixed_epi(c.bias != nullptr, c.bf16, c.act), st, c.plan));
+        return hip_rc(mixq::launch_gemm(p, mixed_epi(c.bias != nullptr, c.bf16, c.act, c.gate_up), st, c.plan));
     }
-    if (c.bias || c.bf16 || c.act) return MIXQ_E_SHAPE;
+    if (c.bias || c.bf16 || c.act || c.gate_up) return MIXQ_E_SHAPE;
     // more outlier columns than one LDS pass holds: the reference's own two-step order (side GEMM into Out, then C = D = Out)
     hipError_t e = mixq::launch_gemm_fp16(c.fpA, c.fpW, c.Out, c.M, c.N, c.O, st);
     if (e != hipSuccess) return MIXQ_E_HIP;
@@ -968,6 +971,25 @@ int mixq_gemm_mixed_act_typed(const int8_t* qA, const int8_t* W, const void* sA,
     if (O > kNumOutliers && (c.act || c.bf16)) return MIXQ_E_SHAPE; // (one LDS pass of outlier columns: no addend form)
     if (qa_layout == MIXQ_QA_FRAGMENT_MAJOR && mixed_frag_gate(c) != MIXQ_OK) return MIXQ_E_SHAPE;
     if (mul && !aligned16(mul)) return MIXQ_E_ALIGN; // (the ping-pong kernels fetch it 16 bytes at a time)
+    return gemm_mixed_impl(c);
+}
+
+// The merged gate / up projection of an MLP: mixq_gemm_mixed_typed's GEMM on (M, 2 N, K) with the merged layer of the header, SiLU(gate) x up in
+// the epilogue of the same launch, Out [M, N].  Plan, K split, scratch and reported name are the plain call's on (M, 2 N, K).  Checks by class.
+int mixq_gemm_mixed_gate_up_typed(const int8_t* qA, const int8_t* W2, const void* sA, const void* sW2, const void* fpA, const void* fpW2,
+                                  void* Out, int M, int N, int K, int O, int qa_layout, int type, void* scratch, size_t scratch_bytes,
+                                  void* stream)
+{
+    if (!type_ok(type)) return MIXQ_E_TYPE;
+    if (!layout_ok(qa_layout)) return MIXQ_E_BADARG;
+    if (M < 0 || N < 0 || K <= 0 || O < 0 || N > INT32_MAX / 2) return MIXQ_E_BADARG;
+    if (M == 0 || N == 0) return MIXQ_OK;
+    MixedCall c = mixed_call(qA, W2, sA, sW2, fpA, fpW2, Out, M, 2 * N, K, O, scratch, scratch_bytes, stream);
+    c.a_frag = qa_layout, c.bf16 = type == MIXQ_TYPE_BF16, c.gate_up = true;
+    const int rc = mixed_args_rc(c); // (null operands; K % 16, O % 8; 2 N % 16 follows from the next line)
+    if (rc != MIXQ_OK) return rc;
+    if (N % 16 || O > kNumOutliers) return MIXQ_E_SHAPE; // (whole blocks of 8 gate + 8 up rows per 32-column MFMA tile; one LDS pass of outlier columns)
+    if (qa_layout == MIXQ_QA_FRAGMENT_MAJOR && mixed_frag_gate(c) != MIXQ_OK) return MIXQ_E_SHAPE;
     return gemm_mixed_impl(c);
 }
 

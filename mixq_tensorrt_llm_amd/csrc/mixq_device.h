@@ -124,6 +124,14 @@ __device__ __forceinline__ uint16_t omul_bits(uint16_t a, uint16_t b)
     else return f2h_bits(h2f(a) * h2f(b));
 }
 
+// merged gate / up projection (EPI_GATE_UP): one output value from the fp32 results of its gate and its up column -- each rounded to the output
+// type (the gate after SiLU), then one multiply of the rounded values: the bits of EPI_DEQUANT for up followed by EPI_DEQUANT_SILU_MUL
+template <bool BF>
+__device__ __forceinline__ uint16_t gate_up_bits(float vg, float vu)
+{
+    return omul_bits<BF>(f2o_bits_of_f32_result<BF>(silu_f32(vg)), f2o_bits_of_f32_result<BF>(vu));
+}
+
 // Two fp32 results -> packed fp16 (RNE), both pinned first (same reason); one v_cvt_pk_f16_f32.
 __device__ __forceinline__ v2h f2h2_of_f32_results(float a, float b)
 {

@@ -50,14 +50,25 @@ enum { EPI_DEQUANT_BF16 = 6, EPI_DEQUANT_BIAS_BF16 = 7 };
 // value, D = g or D = bf16(fp32(g) * fp32(Mul)) -- one multiply of the ROUNDED g by the bf16 [M,N] multiplicand (the fp32 product of two bf16
 // values is exact: one rounding, torch's bf16 multiply).  No addend, no bias, no peer writes, O <= 128.  Kernel choice: the same as EPI_DEQUANT
 enum { EPI_DEQUANT_SILU_BF16 = 8, EPI_DEQUANT_SILU_MUL_BF16 = 9 };
+// 10 / 11: the merged gate / up projection (mixq_gemm_mixed_gate_up_typed), fp16 / bf16: the GEMM is (M, GemmParams::N = 2 n_out, K) on the merged
+// weight of include/mixq.h (blocks of 8 gate rows followed by their 8 up rows); of every 16 GEMM columns the first 8 are EPI_DEQUANT_SILU's g, the
+// last 8 EPI_DEQUANT's u (each rounded to the call's type), and D[m, 8 (c / 16) + c % 8] = T_rn(fp32(g) * fp32(u)) with D [M, n_out] at row stride
+// GemmParams::n_out -- the bits of EPI_DEQUANT for u followed by EPI_DEQUANT_SILU_MUL with Mul = u.  In the 32 x 32 MFMA families gate and up of a
+// column are the same lane's column quads g and g ^ 1 (8 columns apart); in the skinny kernel lanes l and l ^ 32.  No addend, bias or peer writes,
+// O <= 128.  Kernel choice: EPI_DEQUANT's on (M, 2 n_out, K)
+enum { EPI_GATE_UP = 10, EPI_GATE_UP_BF16 = 11 };
+constexpr bool epi_gate_up(int epi) { return epi == EPI_GATE_UP || epi == EPI_GATE_UP_BF16; }
 constexpr bool epi_has_mul(int epi) { return epi == EPI_DEQUANT_SILU_MUL || epi == EPI_DEQUANT_SILU_MUL_BF16; }
 constexpr bool epi_has_silu(int epi) { return epi == EPI_DEQUANT_SILU || epi == EPI_DEQUANT_SILU_BF16 || epi_has_mul(epi); }
 constexpr bool epi_bf16(int epi)
 {
-    return epi == EPI_DEQUANT_BF16 || epi == EPI_DEQUANT_BIAS_BF16 || epi == EPI_DEQUANT_SILU_BF16 || epi == EPI_DEQUANT_SILU_MUL_BF16;
+    return epi == EPI_DEQUANT_BF16 || epi == EPI_DEQUANT_BIAS_BF16 || epi == EPI_DEQUANT_SILU_BF16 || epi == EPI_DEQUANT_SILU_MUL_BF16 ||
+           epi == EPI_GATE_UP_BF16;
 }
+// output column of GEMM column c of a merged gate / up call (c % 16 < 8: the gate column; its up column is c + 8)
+__host__ __device__ constexpr int gate_up_col(int c) { return ((c >> 4) << 3) + (c & 7); }
 constexpr bool epi_bias(int epi) { return epi == EPI_DEQUANT_BIAS || epi == EPI_DEQUANT_BIAS_BF16; }
-// f(std::integral_constant<int, EPI>{}) with the run-time `epi` as a compile-time constant: the eight dequantising epilogues; any other
+// f(std::integral_constant<int, EPI>{}) with the run-time `epi` as a compile-time constant: the ten dequantising epilogues; any other
 // value is EPI_INT32 where the family has that build (INT32), else an error (and f is not instantiated for it)
 template <bool INT32, class F>
 inline hipError_t with_epi(int epi, F&& f)
@@ -71,6 +82,8 @@ inline hipError_t with_epi(int epi, F&& f)
     case EPI_DEQUANT_BIAS_BF16: return f(std::integral_constant<int, EPI_DEQUANT_BIAS_BF16>{});
     case EPI_DEQUANT_SILU_BF16: return f(std::integral_constant<int, EPI_DEQUANT_SILU_BF16>{});
     case EPI_DEQUANT_SILU_MUL_BF16: return f(std::integral_constant<int, EPI_DEQUANT_SILU_MUL_BF16>{});
+    case EPI_GATE_UP: return f(std::integral_constant<int, EPI_GATE_UP>{});
+    case EPI_GATE_UP_BF16: return f(std::integral_constant<int, EPI_GATE_UP_BF16>{});
     }
     if constexpr (INT32) return f(std::integral_constant<int, EPI_INT32>{});
     else return hipErrorInvalidValue;
@@ -125,6 +138,7 @@ struct GemmParams {
                           // launch_gemm split K over 2 / 4 workgroups per 256x256 tile when the tiles alone cover at
                           // most half / a quarter of the CUs (gemm_pp_kernels.hip)
     const uint16_t* bias; // fp16 [N] of EPI_DEQUANT_BIAS (bf16 [N] of EPI_DEQUANT_BIAS_BF16) (added once, by whoever runs the final epilogue of an element), else null
+    int n_out;            // EPI_GATE_UP (_BF16): width and row stride of D = N / 2 (N is the GEMM's width, the merged weight's rows), else 0 (last: the older fields keep their offsets)
 };
 
 // What one int8 GEMM call launches: decided once by plan_gemm (gemm_plan.hip: the ladder of DESIGN.md §4), read by launch_gemm, the

@@ -648,6 +648,34 @@ def gemm_mixed(q, W_int8, x_scale, sW, outliers, fp_weight, M, N, K, bias=None, 
 
 
 @_on_tensor_device
+def gemm_gate_up(q, W2, x_scale, sW2, outliers, fpW2, M, N, K, qa_layout=0, out=None):
+    """MI355X extension (``mixq_gemm_mixed_gate_up_typed``): the gate and the up projection of an MLP as ONE launch,
+    ``silu(gate(x)) * up(x)`` [M, N], on a producer's output (``q``, ``x_scale``, ``outliers`` as ``gemm_mixed`` takes them).  ``W2`` int8
+    [2N, K], ``sW2`` fp16 [2N] and ``fpW2`` [2N, O] are the merged layer of ``pack.merge_gate_up``.  Bit for bit ``gemm_mixed`` on ``up``
+    followed by ``gemm_mixed(act="silu", mul=u)`` on ``gate``, without the [M, N] round trip of ``u``.  fp16 or bf16: the type is
+    ``outliers``' (``x_scale``'s without outlier columns); ``x_scale``, ``fpW2`` and ``out`` must have it, ``sW2`` stays fp16."""
+    O = 0 if outliers is None else int(outliers.shape[-1])
+    dt = _same_dtype(TypeError, "gemm_gate_up", outliers.dtype if O else x_scale.dtype,
+                     "is {got} in a {act} call (x_scale, outliers, fpW2 and out share one type)",
+                     "the activation type is {dt}; fp16 and bf16 are supported",
+                     x_scale=x_scale, fpW2=fpW2 if O else None, out=out)
+    if sW2.dtype != torch.float16 or q.dtype != torch.int8 or W2.dtype != torch.int8:
+        raise TypeError("gemm_gate_up: q and W2 are int8, sW2 is fp16")
+    _dev(*[t for t in (q, W2, x_scale, sW2, outliers if O else None, fpW2 if O else None, out) if t is not None])
+    _rows_fit(x_scale, M, "gemm_gate_up")
+    if W2.numel() != 2 * N * K or sW2.numel() < 2 * N or (O and fpW2.numel() != 2 * N * O):
+        raise ValueError(f"gemm_gate_up: the merged layer of {N} output features has {2 * N} rows (W2 [{2 * N}, {K}], sW2 [{2 * N}], fpW2 [{2 * N}, {O}])")
+    if out is None:
+        out = torch.empty((M, N), dtype=dt, device=q.device)
+    assert out.numel() == M * N
+    scr = None if qa_layout else gemm_scratch(q, M, 2 * N, K)   # (the plain call's on the (M, 2N, K) problem)
+    _lib.check(_lib.load().mixq_gemm_mixed_gate_up_typed(_p(q), _p(W2), _p(x_scale), _p(sW2), _p(outliers) if O else None, _p(fpW2) if O else None,
+                                                         _p(out), M, N, K, O, qa_layout, _type_code(dt), _p(scr),
+                                                         scr.numel() if scr is not None else 0, _st(q)), "gemm_gate_up")
+    return out
+
+
+@_on_tensor_device
 def mixlinear_forward(x, ind, q_weight, scale_col, weight_cache, x_scale, q_layout=0):
     """MixLinear_GEMM.forward (linear.py:163-286, bit = 8, static outlier set) in ONE library call and two launches (MI355X
     extension, include/mixq.h ``mixq_mixlinear_forward_typed``): returns (out [M,N], q_x int8 [M,K], outliers [M,O]); zeroes

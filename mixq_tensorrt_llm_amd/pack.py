@@ -92,3 +92,69 @@ def pack_linear_weights(W: torch.Tensor, act_scales: torch.Tensor, num_outliers:
     Wq = quantize_weight(W, sW)                               # :460-464
     return dict(weight=Wq.numpy(), weights_scaling_factor=sW.numpy(), fp_weight=fp_weight.numpy(),
                 fp_ind=ind.numpy().astype(np.int32), qweight=qweight.numpy(), scales=eetq_scales.numpy())
+
+
+# ---- merged gate / up layer (MI355X extension, include/mixq.h mixq_gemm_mixed_gate_up_typed) ----------------------------------------
+_GATE_UP_KEYS = ("weight", "weights_scaling_factor", "fp_weight")
+
+
+def gate_up_rows(n: int) -> np.ndarray:
+    """Merged row of gate row 0 .. n - 1: ``16 * (i // 8) + i % 8``; the up row of the same feature sits 8 rows further on."""
+    i = np.arange(n, dtype=np.int64)
+    return 16 * (i // 8) + i % 8
+
+
+def _rows_index(t, rows):
+    return torch.from_numpy(rows).to(t.device) if isinstance(t, torch.Tensor) else rows
+
+
+def merge_gate_up(gate: dict, up: dict) -> dict:
+    """The one layer of 2N rows that ``mixlib.gemm_gate_up`` multiplies by, from the packed ``gate`` and ``up`` projections of an MLP
+    (dicts of ``pack_linear_weights``' keys; numpy arrays or torch tensors): ``weight`` int8 [N, K], ``weights_scaling_factor`` fp16 [N]
+    and ``fp_weight`` [N, O] are interleaved in blocks of 8 rows -- merged row ``16 * (n // 8) + n % 8`` holds gate row n, the row 8
+    further on up row n -- and ``fp_ind`` is kept.  Pure indexing; the checkpoint format is unchanged (merge at load time).
+    ``ValueError`` when the layers differ in K, N, a dtype or ``fp_ind``, when N % 16 != 0, or when either has a bias."""
+    for name, d in (("gate", gate), ("up", up)):
+        if d.get("bias") is not None:
+            raise ValueError(f"merge_gate_up: {name} has a bias; the merged epilogue takes none")
+    gi, ui = np.asarray(torch.as_tensor(gate["fp_ind"]).cpu()), np.asarray(torch.as_tensor(up["fp_ind"]).cpu())
+    if gi.shape != ui.shape or not np.array_equal(gi, ui):
+        raise ValueError("merge_gate_up: gate and up have different outlier columns (fp_ind); one producer pass feeds both")
+    n, k = gate["weight"].shape
+    if tuple(up["weight"].shape) != (n, k):
+        raise ValueError(f"merge_gate_up: gate is {n} x {k}, up is {tuple(up['weight'].shape)}")
+    if n % 16:
+        raise ValueError(f"merge_gate_up: out_features = {n} is not a multiple of 16")
+    rows = gate_up_rows(n)
+    out = {}
+    for key in _GATE_UP_KEYS:
+        g, u = gate[key], up[key]
+        if type(g) is not type(u) or g.dtype != u.dtype:
+            raise ValueError(f"merge_gate_up: {key} is {g.dtype} in gate and {u.dtype} in up")
+        if tuple(g.shape) != tuple(u.shape) or g.shape[0] != n:
+            raise ValueError(f"merge_gate_up: {key} is {tuple(g.shape)} in gate and {tuple(u.shape)} in up ({n} rows needed)")
+        shape = (2 * n,) + tuple(g.shape[1:])
+        m = torch.empty(shape, dtype=g.dtype, device=g.device) if isinstance(g, torch.Tensor) else np.empty(shape, dtype=g.dtype)
+        r = _rows_index(g, rows)
+        m[r] = g
+        m[r + 8] = u
+        out[key] = m
+    out["fp_ind"] = gate["fp_ind"]
+    return out
+
+
+def split_gate_up(merged: dict):
+    """The inverse of ``merge_gate_up``: ``(gate, up)`` with ``weight``, ``weights_scaling_factor``, ``fp_weight`` and the shared ``fp_ind``."""
+    n2 = merged["weight"].shape[0]
+    if n2 % 32:
+        raise ValueError(f"split_gate_up: {n2} merged rows are not whole blocks of 8 gate + 8 up rows of an out_features % 16 == 0 layer")
+    rows = gate_up_rows(n2 // 2)
+    gate, up = {}, {}
+    for key in _GATE_UP_KEYS:
+        m = merged[key]
+        if m.shape[0] != n2:
+            raise ValueError(f"split_gate_up: {key} has {m.shape[0]} rows, weight has {n2}")
+        r = _rows_index(m, rows)
+        gate[key], up[key] = m[r], m[r + 8]
+    gate["fp_ind"] = up["fp_ind"] = merged["fp_ind"]
+    return gate, up

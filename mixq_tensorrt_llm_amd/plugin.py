@@ -348,9 +348,39 @@ class MixQLlamaMLP:
         if gate.tp_size > 1 or up.tp_size > 1 or down.tp_size > 1:
             raise ValueError("MixQLlamaMLP: a row-sharded layer (tp_size > 1) has no producer-fed path")
         self.gate, self.up, self.down = gate, up, down
+        self._gate_up = None   # fuse_gate_up(): the merged layer's (W2 int8 [2N, K], sW2 fp16 [2N], fpW2 [2N, 128])
+
+    def fuse_gate_up(self, enable: bool = True):
+        """Opt-in: build the merged gate / up layer once (``pack.merge_gate_up`` on the layers' tensors, 2 N K + more bytes of HBM next to
+        the layers' own), after which ``forward_quantised`` launches ONE GEMM in front of ``down`` (``mixlib.gemm_gate_up``): the same
+        bits, without writing and re-reading ``up(x)``.  Call after the weights are loaded, and again after loading new ones;
+        ``enable=False`` drops the merged tensors.  ``out_features % 16 != 0``: ``ValueError``."""
+        from . import pack
+        self._gate_up = None
+        if not enable:
+            return self
+        g, u = self.gate, self.up
+        if not (g.weight.is_cuda and u.weight.is_cuda):
+            raise _lib.MixQLibraryError("MixQLlamaMLP.fuse_gate_up: the layers live on the CPU; mixlib ops run on the GPU only")
+        if g.fp_weight.dtype != g.dtype or u.fp_weight.dtype != g.dtype:
+            raise TypeError(f"MixQLlamaMLP.fuse_gate_up: a {g.dtype} block with {g.fp_weight.dtype} / {u.fp_weight.dtype} outlier weights")
+        if not torch.equal(g.fp_ind.view(torch.int32), u.fp_ind.view(torch.int32)):
+            raise ValueError("MixQLlamaMLP.fuse_gate_up: gate and up have different outlier columns (fp_ind) now; one producer pass feeds both")
+        m = pack.merge_gate_up(*[dict(weight=l.weight.view(torch.int8), weights_scaling_factor=l.weights_scaling_factor,
+                                      fp_weight=l.fp_weight, fp_ind=l.fp_ind.view(torch.int32)) for l in (g, u)])
+        self._gate_up = (m["weight"].contiguous(), m["weights_scaling_factor"].contiguous(), m["fp_weight"].contiguous())
+        return self
 
     def forward_quantised(self, q, x_scale, outliers, q_layout: int = 0, lead_shape=None) -> torch.Tensor:
-        u = self.up.forward_quantised(q, x_scale, outliers, q_layout)
-        g = self.gate.forward_quantised(q, x_scale, outliers, q_layout, act="silu", mul=u)
+        if self._gate_up is not None:
+            from . import mixlib
+            if outliers.dtype != self.gate.dtype or x_scale.dtype != self.gate.dtype:
+                raise TypeError(f"MixQLlamaMLP.forward_quantised: a {self.gate.dtype} block got {outliers.dtype} outliers and {x_scale.dtype} row scales")
+            W2, sW2, fpW2 = self._gate_up
+            g = mixlib.gemm_gate_up(q, W2, x_scale, sW2, outliers, fpW2, outliers.shape[0], self.gate.out_features, self.gate.in_features,
+                                    qa_layout=q_layout)
+        else:
+            u = self.up.forward_quantised(q, x_scale, outliers, q_layout)
+            g = self.gate.forward_quantised(q, x_scale, outliers, q_layout, act="silu", mul=u)
         y = self.down(g)
         return y if lead_shape is None else y.reshape(*lead_shape, self.down.out_features)
